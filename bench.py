@@ -10,6 +10,21 @@ x (fwd + bwd + penalty-fused Adam) on every node — the full algorithm,
 nothing skipped; metric evaluation runs AFTER the timed window (the
 reference evaluates every 20 rounds outside the round path too).
 
+A plain run sets up, warms up, times exactly --steps rounds and prints
+the result line. --dump-outputs DIR also writes the state the last
+timed round produced. All inputs are seeded, but the kernels accumulate
+gradients with fp64 atomics whose order varies, and training amplifies
+that rounding noise (two runs agree to ~1e-14 after 5 rounds, only to
+~1e-2 after 100). So with --dump-outputs the last timed round starts
+from the parameters and optimizer state saved after the first two
+rounds instead of the previous round's: its result is the same in every
+run up to the rounding of three rounds, and two builds can be compared array for array at any
+--steps. Stepping that follows (--full) goes on from that round. --full
+adds the supplementary measurements: the
+sustained window with its per-step spread and section timing breakdown,
+and the post-timing quality metrics (validation loss/accuracy,
+consensus error) inside "config".
+
 Launch (multi-GPU, by the driver):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
@@ -57,6 +72,20 @@ def parse_args():
         help="mnist workload algorithm (default dinno; dsgd with "
              "--nodes 4 = BASELINE cfg 2)",
     )
+    p.add_argument(
+        "--dump-outputs", default=None, metavar="DIR",
+        help="after the timed steps, write the state the last timed "
+             "round produced (stacked node parameters and the "
+             "algorithm's dual/tracker rows) as DIR/<name>.npy; that "
+             "round then starts from the state saved after the first "
+             "two rounds, so the arrays repeat from run to run",
+    )
+    p.add_argument(
+        "--full", action="store_true",
+        help="also run the supplementary measurements after the timed "
+             "window: the sustained window (per-step spread, section "
+             "timing breakdown) and the post-timing quality metrics",
+    )
     return p.parse_args()
 
 
@@ -101,10 +130,16 @@ def main():
     use_hip = args.engine == "hip" or (
         args.engine == "auto" and device.type == "cuda"
     )
+    if use_hip:
+        _use_built_extension()
     if args.workload == "mnist":
-        pr, step_fn, wl_cfg = _build_mnist(args, device, use_hip)
+        pr, step_fn, wl_cfg, io_fns = _build_mnist(
+            args, device, use_hip
+        )
     else:
-        pr, step_fn, wl_cfg = _build_density(args, device, use_hip)
+        pr, step_fn, wl_cfg, io_fns = _build_density(
+            args, device, use_hip
+        )
 
     def sync():
         if device.type == "cuda":
@@ -114,11 +149,23 @@ def main():
             if device.type == "cuda":
                 torch.cuda.synchronize()
 
+    outputs_fn, state_fn = io_fns
+    # see _Replay: with --dump-outputs the last timed round runs from
+    # the state saved after the first two rounds (a few async device
+    # copies, queued like the round's own launches)
+    replay = None
+    if args.dump_outputs:
+        replay = _Replay(state_fn, args.warmup + args.steps)
+
     for k in range(args.warmup):
+        if replay is not None:
+            replay.before_round(k)
         step_fn(k)
     sync()
     t0 = time.perf_counter()
     for k in range(args.warmup, args.warmup + args.steps):
+        if replay is not None:
+            replay.before_round(k)
         step_fn(k)
     sync()
     elapsed = time.perf_counter() - t0
@@ -130,6 +177,114 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
 
+    if args.dump_outputs:
+        # before any --full extra stepping: the state of the last
+        # timed round, exactly
+        _dump_outputs(args.dump_outputs, outputs_fn(), rank, world)
+
+    sustain_stats, quality, timing_dict = {}, {}, None
+    if args.full:
+        sustain_stats, timing_dict = _sustained_window(
+            args, step_fn, sync, elapsed, world, device
+        )
+
+    if world > 1:
+        import faulthandler
+
+        faulthandler.cancel_dump_traceback_later()
+
+    if args.full:
+        quality = _quality_metrics(pr)
+
+    if rank == 0:
+        rounds_per_sec = args.steps / elapsed
+        out = {
+            "metric": "comm_rounds_per_sec",
+            "value": rounds_per_sec,
+            "unit": "rounds/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": args.dtype,
+            "data": "synthetic",
+            "timed_region_s": round(elapsed, 6),
+            **sustain_stats,
+            "config": {
+                **wl_cfg,
+                "parallelism": f"graph-decentralized dp, "
+                               f"{wl_cfg['nodes']} nodes on "
+                               f"{world} rank(s)",
+                "engine": "hip-stacked" if use_hip else "torch-golden",
+                **quality,
+            },
+        }
+        if timing_dict is not None:
+            td = timing_dict()
+            if td:
+                out["timing_breakdown_ms"] = td
+        print(json.dumps(out), flush=True)
+
+    if dist.is_initialized():
+        dist.destroy_process_group()
+
+
+def _use_built_extension():
+    """Run the HIP extension that the build step left in the tree, as
+    it is: when its source-hash stamp matches the kernel sources, import
+    the shared object directly and hand it to ``ops.get_ext()``. The
+    benchmark then neither compiles nor re-checks the build (no ninja
+    run, no lock file), so it also runs from a tree it cannot write to.
+    Without a matching binary ``get_ext()`` builds one as usual."""
+    import importlib.util
+
+    from nn_distributed_training_amd import ops
+    from nn_distributed_training_amd.ops import build as ext_build
+
+    so = os.path.join(ext_build._BUILD_DIR, ext_build._EXT_NAME + ".so")
+    try:
+        with open(ext_build._HASH_STAMP) as f:
+            stamp = f.read().strip()
+    except OSError:
+        return
+    if stamp != ext_build.source_hash() or not os.path.isfile(so):
+        return
+    spec = importlib.util.spec_from_file_location(ext_build._EXT_NAME, so)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    ops._ext = mod
+
+
+def _dump_outputs(out_dir, tensors, rank, world):
+    """Write what the last timed round produced as ``<name>.npy`` (one
+    file per array; ``<name>_rank<r>.npy`` holds rank r's local node
+    rows when the job is split over several ranks)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        # the headline models are ~28k parameters x 8 nodes (1.8 MB in
+        # fp64); anything that would not fit a 16 MB share of the dump
+        # budget is cut to a fixed seeded sample of its elements
+        cap = (16 << 20) // a.itemsize
+        if a.size > cap:
+            pick = np.random.default_rng(0).choice(
+                a.size, size=cap, replace=False
+            )
+            pick.sort()
+            a = a.reshape(-1)[pick]
+        if world > 1:
+            name = f"{name}_rank{rank}"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def _sustained_window(args, step_fn, sync, elapsed, world, device):
     # ---- sustained window (supplementary evidence; VERDICT r1 weak
     # #4/#7): the headline value above times EXACTLY --steps rounds per
     # the bench contract, but with driver-chosen small K that region can
@@ -186,12 +341,10 @@ def main():
             statistics.pstdev(diffs) if len(diffs) > 1 else 0.0, 4
         ),
     }
+    return sustain_stats, timing_dict
 
-    if world > 1:
-        import faulthandler
 
-        faulthandler.cancel_dump_traceback_later()
-
+def _quality_metrics(pr):
     # post-timing quality metrics (val acc/loss + consensus error)
     pr.evaluate_metrics(at_end=True)
     cons = pr.metrics["consensus_error"][-1][1]
@@ -203,41 +356,7 @@ def main():
     if "validation_loss" in pr.metrics and pr.metrics["validation_loss"]:
         vl = pr.metrics["validation_loss"][-1]
         quality["val_loss_max"] = round(float(vl.amax()), 4)
-
-    if rank == 0:
-        rounds_per_sec = args.steps / elapsed
-        out = {
-            "metric": "comm_rounds_per_sec",
-            "value": rounds_per_sec,
-            "unit": "rounds/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "timed_region_s": round(elapsed, 6),
-            **sustain_stats,
-            "config": {
-                **wl_cfg,
-                "parallelism": f"graph-decentralized dp, "
-                               f"{wl_cfg['nodes']} nodes on "
-                               f"{world} rank(s)",
-                "engine": "hip-stacked" if use_hip else "torch-golden",
-                **quality,
-            },
-        }
-        if timing_dict is not None:
-            td = timing_dict()
-            if td:
-                out["timing_breakdown_ms"] = td
-        print(json.dumps(out), flush=True)
-
-    if dist.is_initialized():
-        dist.destroy_process_group()
+    return quality
 
 
 def _make_graph(args, N):
@@ -322,22 +441,14 @@ def _build_mnist(args, device, use_hip):
         driver = drv_cls(dopt, pr)
         driver.prepare()
         step_fn = driver.step_round
+        io_fns = _stacked_outputs(pr, driver)
     else:
         dopt = build_optimizer(pr, device, opt_conf)
+        io_fns = _golden_outputs(pr, dopt)
         if alg == "dinno":
             step_fn = _golden_round_fn(dopt, pr)
         elif alg == "dsgt":
-            state = {"ready": False}
-
-            def step_fn(k, _d=dopt):
-                if not state["ready"]:
-                    if _d.conf["init_grads"]:
-                        for i in pr.local_nodes:
-                            g = _d._local_grad_vector(i)
-                            _d.y[i] = g.clone()
-                            _d.g[i] = g.clone()
-                    state["ready"] = True
-                _golden_dsgt_round(_d, pr)
+            step_fn = _golden_dsgt_round_fn(dopt, pr)
         else:
             state = {"alph": dopt.alph0}
 
@@ -351,7 +462,84 @@ def _build_mnist(args, device, use_hip):
         "global_batch": B * N,
         "primal_iterations": 2 if alg == "dinno" else None,
     }
-    return pr, step_fn, cfg
+    return pr, step_fn, cfg, io_fns
+
+
+def _stacked_outputs(pr, driver):
+    """What a round of the stacked engine leaves for its caller: the
+    [local nodes, n] parameter stack, plus the DiNNO duals / DSGT
+    gradient tracker that the next round consumes."""
+
+    def outputs():
+        out = {"theta": pr.stacked.theta}
+        if hasattr(driver, "duals"):
+            out["duals"] = driver.duals
+        if hasattr(driver, "y"):
+            out["y"] = driver.y
+        return out
+
+    def state():
+        # every tensor a round reads from the one before it (looked up
+        # per call: DSGT swaps its parameter buffers each round)
+        st = driver._opt_state()
+        return [pr.stacked.theta] + [
+            st[k] for k in sorted(st) if torch.is_tensor(st[k])
+        ]
+
+    return outputs, state
+
+
+def _golden_outputs(pr, opt):
+    """Same arrays, same names, from the golden engine's per-node state."""
+
+    def outputs():
+        out = {"theta": pr.local_params_stack()}
+        for name in ("duals", "y"):
+            rows = getattr(opt, name, None)
+            if rows is not None:
+                out[name] = torch.stack([rows[i] for i in pr.local_nodes])
+        return out
+
+    def state():
+        ts = [p.data for i in pr.local_nodes
+              for p in pr.models[i].parameters()]
+        for name in ("duals", "y", "g"):
+            rows = getattr(opt, name, None)
+            if rows is not None:
+                ts += [rows[i] for i in pr.local_nodes]
+        return ts
+
+    return outputs, state
+
+
+class _Replay:
+    """Seeded starting point for the round that --dump-outputs writes.
+
+    Training amplifies the rounding noise of the kernels' unordered
+    fp64 atomic sums (two runs agree to ~1e-14 after 5 rounds but only
+    to ~1e-2 after 100), so a round that continues from hundreds of
+    earlier ones cannot be compared between runs or builds. With
+    --dump-outputs the last timed round therefore starts from the state
+    captured after the first two rounds (by then the nodes have moved
+    apart and the duals are non-zero; before them every node holds the
+    same parameters and the consensus terms vanish): same kernels,
+    shapes, batch position and round-k schedule as without the option,
+    but inputs that agree between runs to the rounding of two rounds.
+    """
+
+    def __init__(self, state_fn, total_rounds):
+        self.state_fn = state_fn
+        self.last = total_rounds - 1
+        self.capture_at = min(2, self.last)
+        self.saved = None
+
+    def before_round(self, k):
+        if k == self.capture_at:
+            self.saved = [t.detach().clone() for t in self.state_fn()]
+        if k == self.last and k != self.capture_at:
+            with torch.no_grad():
+                for dst, src in zip(self.state_fn(), self.saved):
+                    dst.copy_(src)
 
 
 def _golden_dsgd_round(opt, pr, state):
@@ -452,20 +640,11 @@ def _build_density(args, device, use_hip):
         driver = DSGTStackedDriver(DSGT(pr, device, opt_conf), pr)
         driver.prepare()
         step_fn = driver.step_round
+        io_fns = _stacked_outputs(pr, driver)
     else:
         dopt = DSGT(pr, device, opt_conf)
-        # golden per-round closure (init_grads bootstrap first)
-        state = {"ready": False}
-
-        def step_fn(k, _dopt=dopt):
-            if not state["ready"]:
-                if _dopt.conf["init_grads"]:
-                    for i in pr.local_nodes:
-                        g = _dopt._local_grad_vector(i)
-                        _dopt.y[i] = g.clone()
-                        _dopt.g[i] = g.clone()
-                state["ready"] = True
-            _golden_dsgt_round(_dopt, pr)
+        io_fns = _golden_outputs(pr, dopt)
+        step_fn = _golden_dsgt_round_fn(dopt, pr)
 
     cfg = {
         "model": "FourierNet[2,256,64,64,64,1] n=25601",
@@ -475,7 +654,22 @@ def _build_density(args, device, use_hip):
         "global_batch": B * N,
         "window": 100,
     }
-    return pr, step_fn, cfg
+    return pr, step_fn, cfg, io_fns
+
+
+def _golden_dsgt_round_fn(opt, pr):
+    """Golden per-round closure. The init_grads bootstrap runs here, at
+    setup, as the stacked driver's prepare() does."""
+    if opt.conf["init_grads"]:
+        for i in pr.local_nodes:
+            g = opt._local_grad_vector(i)
+            opt.y[i] = g.clone()
+            opt.g[i] = g.clone()
+
+    def step(k):
+        _golden_dsgt_round(opt, pr)
+
+    return step
 
 
 def _golden_dsgt_round(opt, pr):

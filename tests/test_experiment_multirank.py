@@ -20,12 +20,19 @@ def _worker(rank, td, port):
         WORLD_SIZE="2",
         LOCAL_RANK=str(rank),
     )
+    from datetime import timedelta
+
     import torch.distributed as dist
 
     from nn_distributed_training_amd.experiments.dist_mnist_ex import (
         experiment,
     )
 
+    # this is the gloo/CPU driver test (use_cuda is off in the config):
+    # bring the group up on gloo here, as the driver reuses a group that
+    # is already initialized. Left to its default it would pick RCCL
+    # wherever a GPU is visible, and RCCL refuses two ranks on one device.
+    dist.init_process_group(backend="gloo", timeout=timedelta(seconds=120))
     try:
         experiment(os.path.join(td, "cfg.yaml"))
     finally:

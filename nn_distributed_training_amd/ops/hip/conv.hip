@@ -94,17 +94,22 @@ __global__ void conv_pool_fwd_k(
 // of the chunk, waves shuffle-reduce, wave leaders combine in LDS and
 // lane 0 atomically adds into the grad stack (the caller zeroes the
 // conv slice first).
+//
+// The body takes its block index `bid`, thread index `tid`, block size
+// `nthr` (a multiple of 64, at most 256) and its LDS scratch `red`
+// ([(KMAX*KMAX+1)*4]) as arguments, so the merged backward launch
+// (fused_mnist.hip dw_conv_bwd_k) can run it as one role of a flat grid.
 template <typename T, int KMAX>
-__global__ void conv_pool_bwd_k(
+DEV_INLINE void conv_pool_bwd_body(
     const T* __restrict__ dY, const unsigned char* __restrict__ idx,
     const T* __restrict__ X, T* __restrict__ gstack,
     long n, long w_off, long b_off, int B, int F, int K, int IMG,
     int nchunk,
     const long* __restrict__ src_idx, long idx_stride, long idx_off,
-    long maxlen) {
-  const int chunk = blockIdx.x % nchunk;
-  const int f = (blockIdx.x / nchunk) % F;
-  const int l = blockIdx.x / (nchunk * F);
+    long maxlen, int bid, int tid, int nthr, T* __restrict__ red) {
+  const int chunk = bid % nchunk;
+  const int f = (bid / nchunk) % F;
+  const int l = bid / (nchunk * F);
   const int conv_out = IMG - (K - 1);
   const int P = conv_out / 2;
   const int npool = F * P * P;
@@ -135,16 +140,16 @@ __global__ void conv_pool_bwd_k(
       g = dY[o];
       d = idx[o];
     };
-    long t = threadIdx.x;
+    long t = tid;
     T g = T(0);
     int d = 0;
     long b = 0;
     if (work > 0) hdr(t, g, d, b);
-    for (; t < work; t += blockDim.x) {
+    for (; t < work; t += nthr) {
       T gn;
       int dn;
       long bn;
-      hdr(t + blockDim.x, gn, dn, bn);
+      hdr(t + nthr, gn, dn, bn);
       const int py = (int)((t / P) % P);
       const int px = (int)(t % P);
       const int cy = 2 * py + (d >> 1);
@@ -167,7 +172,7 @@ __global__ void conv_pool_bwd_k(
       b = bn;
     }
   } else {
-    for (int t = threadIdx.x; t < work; t += blockDim.x) {
+    for (int t = tid; t < work; t += nthr) {
       const int b = b0 + t / (P * P);
       const int py = (t / P) % P;
       const int px = t % P;
@@ -204,9 +209,9 @@ __global__ void conv_pool_bwd_k(
   // barrier and the first KMAX*KMAX+1 threads finish their tap in
   // parallel. The previous per-tap LDS tree spent 2 barriers per tap
   // (52 for K=5) and dominated the kernel.
-  __shared__ T red[(KMAX * KMAX + 1) * 4];  // [tap][wave]
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
+  // red: [tap][wave]
+  const int lane = tid & (WAVE - 1);
+  const int wid = tid / WAVE;
   T* wslice = gstack + (long)l * n + w_off + (long)f * K * K;
 #pragma unroll
   for (int i = 0; i < KMAX * KMAX + 1; ++i) {
@@ -217,7 +222,7 @@ __global__ void conv_pool_bwd_k(
     if (lane == 0) red[i * 4 + wid] = v;
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < KMAX * KMAX + 1; i += blockDim.x) {
+  for (int i = tid; i < KMAX * KMAX + 1; i += nthr) {
     const int ky = i / KMAX, kx = i % KMAX;
     const bool is_db = (i == KMAX * KMAX);
     if (!is_db && (ky >= K || kx >= K)) continue;
@@ -229,6 +234,21 @@ __global__ void conv_pool_bwd_k(
       atomicAdd(&wslice[ky * K + kx], tot);
     }
   }
+}
+
+template <typename T, int KMAX>
+__global__ void conv_pool_bwd_k(
+    const T* __restrict__ dY, const unsigned char* __restrict__ idx,
+    const T* __restrict__ X, T* __restrict__ gstack,
+    long n, long w_off, long b_off, int B, int F, int K, int IMG,
+    int nchunk,
+    const long* __restrict__ src_idx, long idx_stride, long idx_off,
+    long maxlen) {
+  __shared__ T red[(KMAX * KMAX + 1) * 4];
+  conv_pool_bwd_body<T, KMAX>(
+      dY, idx, X, gstack, n, w_off, b_off, B, F, K, IMG, nchunk,
+      src_idx, idx_stride, idx_off, maxlen, blockIdx.x, threadIdx.x,
+      blockDim.x, red);
 }
 
 }  // namespace conv

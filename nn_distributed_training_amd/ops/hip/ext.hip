@@ -822,15 +822,75 @@ void conv_pool_bwd_idx(torch::Tensor dY, torch::Tensor idx,
   HIP_CHECK_LAST();
 }
 
-// one-launch fc block: fc1+fc2 fwd, NLL, full fc backward (see
-// fused_mnist.hip fc_block_k). Caller pre-zeroes the grad stack.
-void fc_block(torch::Tensor x0, torch::Tensor theta,
-              torch::Tensor Y_all, torch::Tensor idx, long idx_stride,
-              long idx_off, torch::Tensor grad, torch::Tensor dx0,
-              torch::Tensor dz1g,
-              c10::optional<torch::Tensor> loss, long w1_off,
-              long b1_off, long w2_off, long b2_off, long M, long I,
-              long H, long C, double loss_scale, bool mask_dx0) {
+// true where linear_bwd_dw() above ends in its last branch, the small
+// 16x16-tile store-path kernel (mirrors its branch conditions)
+inline bool dw_takes_small_kernel(long M, long I, long O) {
+  if (M >= 256 && O % 64 == 0 && I % 16 == 0 && I <= 448 && O <= 512) {
+    return false;
+  }
+  if (M >= 256 && I >= 16 && O >= 16) return false;
+  return M <= 2048;
+}
+
+// fc1 dW/db + gather-sourced conv dW/db in ONE launch (fused_mnist.hip
+// dw_conv_bwd_k) where the dW shape takes the small store-path kernel;
+// any other shape keeps the two launches. Same preconditions as
+// linear_bwd_dw + conv_pool_bwd_idx: the conv slice of gstack is zero.
+void dw_conv_bwd_idx(torch::Tensor dZ, torch::Tensor X,
+                     torch::Tensor dY, torch::Tensor pidx,
+                     torch::Tensor X_all, torch::Tensor src_idx,
+                     long idx_stride, long idx_off,
+                     torch::Tensor gstack, long w_off, long b_off,
+                     long M, long I, long O, long cw_off, long cb_off,
+                     long F, long K, long IMG) {
+  if (!dw_takes_small_kernel(M, I, O)) {
+    linear_bwd_dw(dZ, X, gstack, w_off, b_off, M, I, O);
+    conv_pool_bwd_idx(dY, pidx, X_all, src_idx, idx_stride, idx_off,
+                      gstack, cw_off, cb_off, M, F, K, IMG);
+    return;
+  }
+  CHECK_DEV(dZ); CHECK_DEV(X); CHECK_DEV(dY); CHECK_DEV(X_all);
+  CHECK_DEV(gstack);
+  const long L = gstack.size(0), n = gstack.size(1);
+  const long maxlen = X_all.size(1);
+  TORCH_CHECK(K <= 7, "conv_pool_bwd supports kernel size <= 7");
+  const int nchunk = (int)std::min<long>(M, 32);
+  const long gx = (I + 15) / 16, gy = (O + 15) / 16;
+  const long n_dw = gx * gy * L;
+  const long n_cv = L * F * nchunk;
+  DISPATCH_FT(dZ, {
+    if (K <= 5) {
+      hipLaunchKernelGGL((fmnist::dw_conv_bwd_k<scalar_t, 5>),
+          dim3(n_dw + n_cv), dim3(256), 0, cur_stream(),
+          dZ.data_ptr<scalar_t>(), X.data_ptr<scalar_t>(), w_off, b_off,
+          (int)M, (int)I, (int)O, (int)gx, (int)gy, (int)n_dw,
+          dY.data_ptr<scalar_t>(), pidx.data_ptr<unsigned char>(),
+          X_all.data_ptr<scalar_t>(), cw_off, cb_off, (int)F, (int)K,
+          (int)IMG, nchunk, src_idx.data_ptr<long>(), idx_stride,
+          idx_off, maxlen, gstack.data_ptr<scalar_t>(), n);
+    } else {
+      hipLaunchKernelGGL((fmnist::dw_conv_bwd_k<scalar_t, 7>),
+          dim3(n_dw + n_cv), dim3(256), 0, cur_stream(),
+          dZ.data_ptr<scalar_t>(), X.data_ptr<scalar_t>(), w_off, b_off,
+          (int)M, (int)I, (int)O, (int)gx, (int)gy, (int)n_dw,
+          dY.data_ptr<scalar_t>(), pidx.data_ptr<unsigned char>(),
+          X_all.data_ptr<scalar_t>(), cw_off, cb_off, (int)F, (int)K,
+          (int)IMG, nchunk, src_idx.data_ptr<long>(), idx_stride,
+          idx_off, maxlen, gstack.data_ptr<scalar_t>(), n);
+    }
+  });
+  HIP_CHECK_LAST();
+}
+
+// the fc_block_k launch alone (fc1 dW/db are the caller's)
+void fc_block_launch(torch::Tensor x0, torch::Tensor theta,
+                     torch::Tensor Y_all, torch::Tensor idx,
+                     long idx_stride, long idx_off, torch::Tensor grad,
+                     torch::Tensor dx0, torch::Tensor dz1g,
+                     c10::optional<torch::Tensor> loss, long w1_off,
+                     long b1_off, long w2_off, long b2_off, long M,
+                     long I, long H, long C, double loss_scale,
+                     bool mask_dx0) {
   CHECK_DEV(x0); CHECK_DEV(theta); CHECK_DEV(grad); CHECK_DEV(dx0);
   CHECK_DEV(dz1g);
   const long L = theta.size(0), n = theta.size(1);
@@ -849,10 +909,63 @@ void fc_block(torch::Tensor x0, torch::Tensor theta,
         (int)C, (scalar_t)loss_scale, mask_dx0 ? 1 : 0);
   });
   HIP_CHECK_LAST();
+}
+
+// one-launch fc block: fc1+fc2 fwd, NLL, full fc backward (see
+// fused_mnist.hip fc_block_k). Caller pre-zeroes the grad stack.
+void fc_block(torch::Tensor x0, torch::Tensor theta,
+              torch::Tensor Y_all, torch::Tensor idx, long idx_stride,
+              long idx_off, torch::Tensor grad, torch::Tensor dx0,
+              torch::Tensor dz1g,
+              c10::optional<torch::Tensor> loss, long w1_off,
+              long b1_off, long w2_off, long b2_off, long M, long I,
+              long H, long C, double loss_scale, bool mask_dx0) {
+  fc_block_launch(x0, theta, Y_all, idx, idx_stride, idx_off, grad,
+                  dx0, dz1g, loss, w1_off, b1_off, w2_off, b2_off, M, I,
+                  H, C, loss_scale, mask_dx0);
   // fc1 dW/db from the exported dz1 (store-path kernel: overwrite,
   // no atomics)
   linear_bwd_dw(dz1g, x0, grad, w1_off, b1_off, M, I, H);
 }
+
+// One native call per forward+backward of the conv -> fc1 -> fc2 -> NLL
+// model on the index-sourced path: conv forward, the fc block, then
+// the merged fc1-dW + conv-backward launch, all on the current stream.
+// At ~10 us of host time per pybind call the three separate calls no
+// longer hid under the iteration's GPU time. Caller pre-zeroes the
+// grad stack (and the loss slot).
+void mnist_fwd_bwd(torch::Tensor X_all, torch::Tensor src_idx,
+                   long idx_stride, long idx_off, torch::Tensor theta,
+                   torch::Tensor Y_all, torch::Tensor x0,
+                   torch::Tensor pidx, torch::Tensor grad,
+                   torch::Tensor dx0, torch::Tensor dz1g,
+                   c10::optional<torch::Tensor> loss, long cw_off,
+                   long cb_off, long F, long K, long IMG, long w1_off,
+                   long b1_off, long w2_off, long b2_off, long M, long I,
+                   long H, long C, double loss_scale) {
+  conv_pool_fwd_idx(X_all, src_idx, idx_stride, idx_off, theta, x0,
+                    pidx, cw_off, cb_off, M, F, K, IMG);
+  fc_block_launch(x0, theta, Y_all, src_idx, idx_stride, idx_off, grad,
+                  dx0, dz1g, loss, w1_off, b1_off, w2_off, b2_off, M, I,
+                  H, C, loss_scale, true);
+  dw_conv_bwd_idx(dz1g, x0, dx0, pidx, X_all, src_idx, idx_stride,
+                  idx_off, grad, w1_off, b1_off, M, I, H, cw_off, cb_off,
+                  F, K, IMG);
+}
+
+#ifdef NDTA_FC_PHASE_CLOCK
+// diagnostic build only: [blocks, 8] wall_clock64 stamps of the last
+// fc_block launch (see fused_mnist.hip FC_STAMP)
+torch::Tensor fc_phase_clock() {
+  auto t = torch::zeros({fmnist::FC_CLK_BLOCKS, 8}, torch::kLong);
+  const hipError_t err = hipMemcpyFromSymbol(
+      t.data_ptr(), HIP_SYMBOL(fmnist::fc_phase_stamps),
+      sizeof(unsigned long long) * fmnist::FC_CLK_BLOCKS * 8);
+  TORCH_CHECK(err == hipSuccess, "fc_phase_clock: ",
+              hipGetErrorString(err));
+  return t;
+}
+#endif
 
 // consensus-error metric: normalized pairwise distances + distance to
 // the normalized mean (reference dist_mnist_problem.py:152-175) on the
@@ -1083,6 +1196,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("feistel_perm", &feistel_perm);
   mod.def("consensus_cdist", &consensus_cdist);
   mod.def("fc_block", &fc_block);
+  mod.def("dw_conv_bwd_idx", &dw_conv_bwd_idx);
+  mod.def("mnist_fwd_bwd", &mnist_fwd_bwd);
+#ifdef NDTA_FC_PHASE_CLOCK
+  mod.def("fc_phase_clock", &fc_phase_clock);
+#endif
   mod.def("fwd_chain", &fwd_chain);
   mod.def("bwd_chain", &bwd_chain);
 }

@@ -346,6 +346,39 @@ __global__ __launch_bounds__(256) void mnist_train_step_k(
 // Requires H <= 64, C <= 16; fc grad slices accumulate atomically
 // (caller zeroes the whole grad stack).
 constexpr int FC_RT = 16;
+
+// Diagnostic phase clock (compiled out unless the extension is built
+// with NDTA_BUILD_DEFINES=-DNDTA_FC_PHASE_CLOCK): thread 0 of each
+// block stamps wall_clock64() (100 MHz) at the phase boundaries into
+// fc_phase_stamps[block][slot]; ext.fc_phase_clock() reads them back.
+// The diagnostic build adds one barrier before the last stamp so slot 5
+// is the block's end, not wave 0's.
+#ifdef NDTA_FC_PHASE_CLOCK
+constexpr int FC_CLK_BLOCKS = 256;
+__device__ unsigned long long fc_phase_stamps[FC_CLK_BLOCKS * 8];
+#define FC_STAMP(slot)                                              \
+  do {                                                              \
+    if (threadIdx.x == 0) {                                         \
+      const int b_ = blockIdx.z * gridDim.x + blockIdx.x;           \
+      if (b_ < FC_CLK_BLOCKS) {                                     \
+        fc_phase_stamps[b_ * 8 + (slot)] = wall_clock64();          \
+      }                                                             \
+    }                                                               \
+  } while (0)
+#else
+#define FC_STAMP(slot) do {} while (0)
+#endif
+constexpr int FC_W2S = 65;  // padded LDS row stride of W2
+
+// one 16-column strip of the dX0 pass: W1[0:64, ix:ix+16] as 16 MFMA B
+// operands plus the x0 values that carry the conv relu' mask for the
+// lane's four output elements
+template <typename T>
+struct fc_strip_t {
+  T w[16];
+  T xm[4];
+};
+
 template <typename T>
 __global__ __launch_bounds__(512) void fc_block_k(
     const T* __restrict__ x0,        // [L*M, I] conv/pool output
@@ -356,31 +389,34 @@ __global__ __launch_bounds__(512) void fc_block_k(
     T* __restrict__ grad,            // [L, n]
     T* __restrict__ dx0,             // [L*M, I]
     T* __restrict__ dz1g,            // [L*M, H] dz1 out (fc1 dW/db
-                                     // run in linear_bwd_dw: the
-                                     // in-kernel atomic dW1 was ~884K
-                                     // f64 atomics/launch)
+                                     // run on the store-path dw
+                                     // kernel: the in-kernel atomic dW1
+                                     // was ~884K f64 atomics/launch)
     T* __restrict__ loss,            // nullable [L]
     long n, long w1_off, long b1_off, long w2_off, long b2_off,
     int M, int I, int H, int C, T loss_scale, int mask_dx0) {
-  // v2: 512 threads = 4 CONSUMER waves (MFMA) + 4 PRODUCER waves
-  // (HBM -> double-buffered LDS). W1's 221 KB/block stream was the
-  // serial chain of the 256-thread version (stage, barrier, MFMA,
-  // barrier x14): wave specialization keeps the stream entirely off
-  // the compute path.
+  // 512 threads = 4 CONSUMER waves (MFMA) + 4 PRODUCER waves (HBM ->
+  // double-buffered LDS) for the fc1 forward: W1's 221 KB/block stream
+  // was the serial chain of the 256-thread version (stage, barrier,
+  // MFMA, barrier x14); wave specialization keeps the stream off the
+  // compute path. All 8 waves then share the log-softmax (one (row,
+  // class) per thread) and the dX0 strips, whose first W1 loads are
+  // issued before the fc2 phases so they land under them.
   using MF = gmfma::mfma_t<T>;
   using acc_t = typename MF::acc_t;
+  using strip_t = fc_strip_t<T>;
   typedef T vec2 __attribute__((ext_vector_type(2)));
   constexpr int RT = FC_RT;
 
   // single LDS arena (trap 4a)
   __shared__ T lds[2 * 32 * (RT + 1) + 2 * 32 * 65 + 2 * RT * 65 +
-                   RT * 17 + 16 * 64 + 16];
+                   RT * 17 + 16 * FC_W2S + 16];
   T* As = lds;                             // [2][32][RT+1]
   T* Bs = As + 2 * 32 * (RT + 1);          // [2][32][65]
   T* y1s = Bs + 2 * 32 * 65;               // [RT][65]
   T* dz1s = y1s + RT * 65;                 // [RT][65]
   T* dz2s = dz1s + RT * 65;                // [RT][17]
-  T* w2s = dz2s + RT * 17;                 // [C*H + C]
+  T* w2s = dz2s + RT * 17;                 // [C][65] | b2 at [16*65]
 
   const long l = blockIdx.z;
   const int m0 = blockIdx.x * RT;
@@ -395,10 +431,17 @@ __global__ __launch_bounds__(512) void fc_block_k(
   const int lk = lane >> 4;
   const bool fullm = (m0 + RT) <= M;
   const int nst = (I + 31) / 32;
+  const T* x0b = x0 + (long)(l * (long)M + m0) * I;  // block's rows
 
-  // P0: W2 + b2 into LDS
-  for (int t = tid; t < C * H; t += 512) w2s[t] = th[w2_off + t];
-  for (int t = tid; t < C; t += 512) w2s[C * H + t] = th[b2_off + t];
+  FC_STAMP(0);
+  // P0: W2 (row stride 65: the logit dots walk it by class) + b2
+  for (int t = tid; t < C * H; t += 512) {
+    w2s[(t / H) * FC_W2S + t % H] = th[w2_off + t];
+  }
+  for (int t = tid; t < C; t += 512) {
+    w2s[16 * FC_W2S + t] = th[b2_off + t];
+  }
+  FC_STAMP(1);
 
   // producer staging: 256 threads cover the [32 k][RT m] x0 image
   // (1 vec2 pair each) and the [32 k][64 o] W1 image (4 pairs)
@@ -472,6 +515,45 @@ __global__ __launch_bounds__(512) void fc_block_k(
     }
     __syncthreads();
   }
+
+  // dX0 strips (P4) are dealt round-robin to the waves as well; the
+  // first two strips' W1 columns and x0 mask values do not depend on
+  // anything computed here, so they load now and land under P2/P3.
+  const int nstrip = (I + 15) / 16;
+  const auto ldstrip = [&](int s, strip_t& st) {
+    if (s >= nstrip) return;  // wave-uniform
+    const int i = s * 16 + lo;
+    if (H == 64 && s * 16 + 16 <= I && fullm) {  // guard-free (4c)
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        st.w[t] = W1[(long)(4 * t + lk) * I + i];
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        st.xm[r] = mask_dx0
+                       ? x0b[(long)MF::acc_row(lane, r) * I + i]
+                       : T(1);
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        st.w[t] = ((4 * t + lk) < H && i < I)
+                      ? W1[(long)(4 * t + lk) * I + i]
+                      : T(0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = MF::acc_row(lane, r);
+        st.xm[r] = !mask_dx0 ? T(1)
+                   : (m0 + m < M && i < I) ? x0b[(long)m * I + i]
+                                           : T(0);
+      }
+    }
+  };
+  strip_t sa, sb;
+  ldstrip(wid, sa);
+  ldstrip(wid + 8, sb);
+
   // y1 = relu(z1 + b1) into LDS (never stored to HBM)
   if (!producer && o0w < H) {
 #pragma unroll
@@ -483,64 +565,65 @@ __global__ __launch_bounds__(512) void fc_block_k(
     }
   }
   __syncthreads();
+  FC_STAMP(2);
 
-  // P2: fc2 logits + row log-softmax + NLL dZ2 (H==64 unrolls the
-  // dot loop 8-wide so the LDS loads batch)
-  if (H == 64) {
-    for (int t = tid; t < RT * C; t += 512) {
-      const int m = t / C, c = t % C;
-      T z = w2s[C * 64 + c];  // b2
-      T part[8] = {};
+  // P2: fc2 logits + log-softmax + NLL dZ2, one (row, class) per
+  // thread: row m's classes sit in 16 adjacent lanes, so the row max
+  // and the row sum are 4 xor-shuffles each and every exp runs once.
+  if (tid < RT * 16) {  // waves 0-3, wave-uniform
+    const int m = tid >> 4, c = tid & 15;
+    const bool act = c < C;
+    const bool rowok = (m0 + m) < M;
+    T z = -INFINITY;
+    if (act) {
+      z = w2s[16 * FC_W2S + c];  // b2
+      if (H == 64) {  // 8 partial sums so the LDS loads batch
+        T part[8] = {};
 #pragma unroll
-      for (int hq = 0; hq < 8; ++hq) {
+        for (int hq = 0; hq < 8; ++hq) {
 #pragma unroll
-        for (int hh = 0; hh < 8; ++hh) {
-          const int h = hq * 8 + hh;
-          part[hh] += y1s[m * 65 + h] * w2s[c * 64 + h];
+          for (int hh = 0; hh < 8; ++hh) {
+            const int h = hq * 8 + hh;
+            part[hh] += y1s[m * 65 + h] * w2s[c * FC_W2S + h];
+          }
+        }
+#pragma unroll
+        for (int hh = 0; hh < 8; ++hh) z += part[hh];
+      } else {
+        for (int h = 0; h < H; ++h) {
+          z += y1s[m * 65 + h] * w2s[c * FC_W2S + h];
         }
       }
+    }
+    T mx = z;
 #pragma unroll
-      for (int hh = 0; hh < 8; ++hh) z += part[hh];
-      dz2s[m * 17 + c] = z;
+    for (int off = 8; off > 0; off >>= 1) {
+      const T o = __shfl_xor(mx, off, 16);
+      mx = o > mx ? o : mx;
     }
-  } else {
-    for (int t = tid; t < RT * C; t += 512) {
-      const int m = t / C, c = t % C;
-      T z = w2s[C * H + c];
-      for (int h = 0; h < H; ++h) {
-        z += y1s[m * 65 + h] * w2s[c * H + h];
-      }
-      dz2s[m * 17 + c] = z;
+    const T e = act ? ::exp(z - mx) : T(0);
+    T sum = e;
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) {
+      sum += __shfl_xor(sum, off, 16);
     }
-  }
-  __syncthreads();
-  if (tid < RT) {
-    const int m = tid;
-    if (m0 + m < M) {
-      const long tgt =
-          Y_all[l * maxlen + idx[l * idx_stride + idx_off + m0 + m]];
-      T mx = dz2s[m * 17];
-      for (int c = 1; c < C; ++c) {
-        mx = dz2s[m * 17 + c] > mx ? dz2s[m * 17 + c] : mx;
+    if (act) {
+      T dz = T(0);
+      if (rowok) {
+        const int tgt = (int)
+            Y_all[l * maxlen + idx[l * idx_stride + idx_off + m0 + m]];
+        dz = (e / sum - (c == tgt ? T(1) : T(0))) *
+             (loss_scale / T(M));
+        if (c == tgt && loss != nullptr) {
+          const T lse = mx + ::log(sum);
+          atomicAdd(&loss[l], -(z - lse) / T(M));
+        }
       }
-      T sum = T(0);
-      for (int c = 0; c < C; ++c) sum += ::exp(dz2s[m * 17 + c] - mx);
-      const T lse = mx + ::log(sum);
-      const T w = loss_scale / T(M);
-      if (loss != nullptr) {
-        atomicAdd(&loss[l], -(dz2s[m * 17 + (int)tgt] - lse) / T(M));
-      }
-      for (int c = 0; c < C; ++c) {
-        dz2s[m * 17 + c] =
-            (::exp(dz2s[m * 17 + c] - lse) - (c == (int)tgt ? T(1)
-                                                            : T(0)))
-            * w;
-      }
-    } else {
-      for (int c = 0; c < C; ++c) dz2s[m * 17 + c] = T(0);
+      dz2s[m * 17 + c] = dz;
     }
   }
   __syncthreads();
+  FC_STAMP(3);
 
   // P3: dz1 = (dz2 @ W2) * relu'(y1) -> LDS + global (fc1 dW/db run
   // on the store-path dw kernel); fc2 dW/db
@@ -548,7 +631,7 @@ __global__ __launch_bounds__(512) void fc_block_k(
     const int m = t / H, h = t % H;
     T s = T(0);
     for (int c = 0; c < C; ++c) {
-      s += dz2s[m * 17 + c] * w2s[c * H + h];
+      s += dz2s[m * 17 + c] * w2s[c * FC_W2S + h];
     }
     const T v = y1s[m * 65 + h] > T(0) ? s : T(0);
     dz1s[m * 65 + h] = v;
@@ -577,57 +660,89 @@ __global__ __launch_bounds__(512) void fc_block_k(
     atomicAdd(&grad[l * n + b2_off + c], s);
   }
   __syncthreads();
+  FC_STAMP(4);
 
   // P4: dX0 = dz1 @ W1 with the conv relu' mask. A[m][k=o] from LDS,
-  // B[k=o][i] = W1 direct from global (coalesced); the 64-wide
-  // i-chunks split between the two wave HALVES (half h takes chunks
-  // h, h+2, ...), each half prefetching its next chunk's W1 column
-  // block while the current chunk's MFMAs issue.
-  {
-    const int half = wid >> 2;   // 0 or 1
-    const int wq = wid & 3;      // wave within the half
-    T w1v[16], w1n[16];
-    const auto ldw1 = [&](int ixv, T* dst) {
-      if (H == 64 && ixv + 16 <= I) {  // guard-free (trap 4c)
+  // B[k=o][i] = the strip's W1 columns, already in registers. Wave w
+  // owns strips w, w+8, ...; as soon as a slot's MFMAs have issued it
+  // reloads with the strip two ahead, so a wave always has its next
+  // strip complete or in flight. Two accumulators halve the MFMA
+  // dependency chain.
+  const auto dx_strip = [&](int s, const strip_t& st) {
+    acc_t ax0 = {}, ax1 = {};
 #pragma unroll
-        for (int t = 0; t < 16; ++t) {
-          dst[t] = W1[(long)(4 * t + lk) * I + ixv + lo];
-        }
-      } else {
+    for (int t = 0; t < 16; t += 2) {
+      ax0 = MF::mma(dz1s[lo * 65 + 4 * t + lk], st.w[t], ax0);
+      ax1 = MF::mma(dz1s[lo * 65 + 4 * t + 4 + lk], st.w[t + 1], ax1);
+    }
+    const int i = s * 16 + lo;
 #pragma unroll
-        for (int t = 0; t < 16; ++t) {
-          dst[t] = ((4 * t + lk) < H && ixv + lo < I)
-                       ? W1[(long)(4 * t + lk) * I + ixv + lo]
-                       : T(0);
-        }
-      }
-    };
-    const int i0_first = half * 64;
-    if (i0_first < I) {
-      ldw1(i0_first + wq * 16, w1v);
-      for (int i0 = i0_first; i0 < I; i0 += 128) {
-        const int ix = i0 + wq * 16;
-        if (i0 + 128 < I) ldw1(i0 + 128 + wq * 16, w1n);
-        acc_t ax = {};
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-          const T a = dz1s[lo * 65 + 4 * t + lk];
-          ax = MF::mma(a, w1v[t], ax);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + MF::acc_row(lane, r);
-          const int i = ix + lo;
-          if (m < M && i < I) {
-            const long off = (long)(l * (long)M + m) * I + i;
-            // conv relu' mask: x0 IS the conv block's relu output
-            dx0[off] = (!mask_dx0 || x0[off] > T(0)) ? ax[r] : T(0);
-          }
-        }
-#pragma unroll
-        for (int t = 0; t < 16; ++t) w1v[t] = w1n[t];
+    for (int r = 0; r < 4; ++r) {
+      const int m = MF::acc_row(lane, r);
+      if (m0 + m < M && i < I) {
+        // conv relu' mask: x0 IS the conv block's relu output
+        dx0[(long)(l * (long)M + m0 + m) * I + i] =
+            st.xm[r] > T(0) ? ax0[r] + ax1[r] : T(0);
       }
     }
+  };
+  for (int s = wid; s < nstrip; s += 16) {
+    dx_strip(s, sa);
+    ldstrip(s + 16, sa);
+    if (s + 8 < nstrip) dx_strip(s + 8, sb);
+    ldstrip(s + 24, sb);
+  }
+#ifdef NDTA_FC_PHASE_CLOCK
+  __syncthreads();
+  FC_STAMP(5);
+#endif
+}
+
+// ---------------------------------------------------------------------
+// Merged backward launch: fc1 dW/db (gemm::linear_bwd_dw_body) and the
+// gather-sourced conv dW/db (conv::conv_pool_bwd_body) as two roles of
+// one flat grid of 256-thread blocks. Both only read what fc_block_k
+// produced (dz1 + x0 for one, dx0 + the pool argmax for the other) and
+// write disjoint slices of the grad stack, so as separate launches the
+// 7.8 us dW kernel sat in a serial slot of its own; in one grid the 864
+// dW blocks of the MNIST shape share the chip with the 768 conv blocks.
+// Blocks [0, n_dw) decode to the dW kernel's (bx, by, bz) grid, the
+// rest to the conv kernel's block index; the role branch is
+// block-uniform and the LDS arena is the larger of the two needs.
+// No occupancy bound beyond the block size: the conv role needs ~100
+// VGPRs in fp64 (4 blocks/CU) and forcing 8 waves/SIMD spills its dW
+// accumulators to scratch. The short dW blocks come first in the grid
+// and retire quickly, so the conv blocks fill in behind them.
+template <typename T, int KMAX>
+__global__ __launch_bounds__(256) void dw_conv_bwd_k(
+    // dW role
+    const T* __restrict__ dZ, const T* __restrict__ X,
+    long w_off, long b_off, int M, int I, int O, int dw_gx, int dw_gy,
+    int n_dw,
+    // conv role
+    const T* __restrict__ dY, const unsigned char* __restrict__ pidx,
+    const T* __restrict__ X_all, long cw_off, long cb_off, int F, int K,
+    int IMG, int nchunk, const long* __restrict__ src_idx,
+    long idx_stride, long idx_off, long maxlen,
+    T* __restrict__ gstack, long n) {
+  constexpr int DW_LDS = 2 * gemm::TILE * (gemm::TILE + 1);
+  constexpr int CV_LDS = (KMAX * KMAX + 1) * 4;
+  __shared__ T smem[DW_LDS > CV_LDS ? DW_LDS : CV_LDS];
+  const int bid = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (bid < n_dw) {
+    const int bx = bid % dw_gx;
+    const int by = (bid / dw_gx) % dw_gy;
+    const long bz = bid / (dw_gx * dw_gy);
+    gemm::linear_bwd_dw_body<T>(
+        dZ, X, gstack, n, w_off, b_off, M, I, O, bx, by, bz,
+        tid / gemm::TILE, tid % gemm::TILE, smem,
+        smem + gemm::TILE * (gemm::TILE + 1));
+  } else {
+    conv::conv_pool_bwd_body<T, KMAX>(
+        dY, pidx, X_all, gstack, n, cw_off, cb_off, M, F, K, IMG,
+        nchunk, src_idx, idx_stride, idx_off, maxlen, bid - n_dw, tid,
+        256, smem);
   }
 }
 

@@ -206,20 +206,24 @@ __global__ void linear_bwd_dx_k(
 // at the layer's offset; db[O] (column sums of dZ) is fused: the i0==0
 // block column accumulates bias partials from its staged dZ tiles while
 // it loops over M (the separate bias kernel was an underfilled launch).
+// The body takes its block (bx, by, bz) and thread (to, ti) coordinates
+// and its two [TILE][TILE+1] LDS tiles as arguments, so the merged
+// backward launch (fused_mnist.hip dw_conv_bwd_k) can run it as one
+// role of a flat grid; the summation order is the same wherever it is
+// called from.
 template <typename T>
-__global__ void linear_bwd_dw_k(
+DEV_INLINE void linear_bwd_dw_body(
     const T* __restrict__ dZ, const T* __restrict__ X,
     T* __restrict__ gstack, long n, long w_off, long b_off,
-    int M, int I, int O) {
-  __shared__ T gs[TILE][TILE + 1];
-  __shared__ T xs[TILE][TILE + 1];
-  const long l = blockIdx.z;
+    int M, int I, int O, int bx, int by, long bz, int to, int ti,
+    T* __restrict__ gs, T* __restrict__ xs) {
+  constexpr int TP = TILE + 1;
+  const long l = bz;
   const T* dZl = dZ + l * (long)M * O;
   const T* Xl = X + l * (long)M * I;
 
-  const int o0 = blockIdx.y * TILE;
-  const int i0 = blockIdx.x * TILE;
-  const int to = threadIdx.y, ti = threadIdx.x;
+  const int o0 = by * TILE;
+  const int i0 = bx * TILE;
   const bool bias_block = (i0 == 0);
 
   T acc = T(0);
@@ -228,16 +232,16 @@ __global__ void linear_bwd_dw_k(
     {
       const int m = k0 + to;
       const int o = o0 + ti;
-      gs[to][ti] = (m < M && o < O) ? dZl[(long)m * O + o] : T(0);
+      gs[to * TP + ti] = (m < M && o < O) ? dZl[(long)m * O + o] : T(0);
       const int i = i0 + ti;
-      xs[to][ti] = (m < M && i < I) ? Xl[(long)m * I + i] : T(0);
+      xs[to * TP + ti] = (m < M && i < I) ? Xl[(long)m * I + i] : T(0);
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < TILE; ++k) {
-      acc += gs[k][to] * xs[k][ti];
+      acc += gs[k * TP + to] * xs[k * TP + ti];
     }
-    if (bias_block) bacc += gs[to][ti];
+    if (bias_block) bacc += gs[to * TP + ti];
     __syncthreads();
   }
   const int o = o0 + to, i = i0 + ti;
@@ -246,15 +250,27 @@ __global__ void linear_bwd_dw_k(
   }
   if (bias_block) {
     // column-sum bacc over to (16 rows) through LDS, thread row 0 writes
-    gs[to][ti] = bacc;
+    gs[to * TP + ti] = bacc;
     __syncthreads();
     if (to == 0 && o0 + ti < O) {
       T s = T(0);
 #pragma unroll
-      for (int r = 0; r < TILE; ++r) s += gs[r][ti];
+      for (int r = 0; r < TILE; ++r) s += gs[r * TP + ti];
       gstack[l * n + b_off + o0 + ti] = s;
     }
   }
+}
+
+template <typename T>
+__global__ void linear_bwd_dw_k(
+    const T* __restrict__ dZ, const T* __restrict__ X,
+    T* __restrict__ gstack, long n, long w_off, long b_off,
+    int M, int I, int O) {
+  __shared__ T gs[TILE * (TILE + 1)];
+  __shared__ T xs[TILE * (TILE + 1)];
+  linear_bwd_dw_body<T>(dZ, X, gstack, n, w_off, b_off, M, I, O,
+                        blockIdx.x, blockIdx.y, blockIdx.z,
+                        threadIdx.y, threadIdx.x, gs, xs);
 }
 
 // M-chunked dW+db for skinny layers (I or O < 16, e.g. the FourierNet

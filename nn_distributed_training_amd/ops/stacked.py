@@ -645,12 +645,6 @@ class StackedEngine:
                 self.sampler, "stream") else self.sampler.buf
             stride = self.sampler.S if hasattr(
                 self.sampler, "S") else self.B
-            ext.conv_pool_fwd_idx(
-                self.X_all, idx_t, stride, self._last_off,
-                self.theta, bufs["acts"][0], bufs["idxs"][0],
-                conv.w_off, conv.b_off, M, conv.out_dim,
-                conv.kernel_size, conv.in_dim,
-            )
             # fc grads accumulate atomically: the stack must be all
             # zeros here. The step kernels clear it as they consume it
             # (zero_grad), so the fill launch is usually skipped.
@@ -661,19 +655,15 @@ class StackedEngine:
             if want_loss:
                 bufs["loss"].zero_()
                 loss_buf = bufs["loss"]
-            ext.fc_block(
-                bufs["acts"][0], self.theta, self.Y_all, idx_t,
-                stride, self._last_off, self.grad, bufs["dzs"][0],
-                bufs["dzs"][1],
-                loss_buf, fc1.w_off, fc1.b_off, fc2.w_off, fc2.b_off,
+            # conv fwd -> fc block -> merged fc1-dW + conv bwd launch,
+            # one native call (ext.hip mnist_fwd_bwd)
+            ext.mnist_fwd_bwd(
+                self.X_all, idx_t, stride, self._last_off, self.theta,
+                self.Y_all, bufs["acts"][0], bufs["idxs"][0], self.grad,
+                bufs["dzs"][0], bufs["dzs"][1], loss_buf,
+                conv.w_off, conv.b_off, conv.out_dim, conv.kernel_size,
+                conv.in_dim, fc1.w_off, fc1.b_off, fc2.w_off, fc2.b_off,
                 M, fc1.in_dim, fc1.out_dim, fc2.out_dim, loss_scale,
-                True,
-            )
-            ext.conv_pool_bwd_idx(
-                bufs["dzs"][0], bufs["idxs"][0], self.X_all, idx_t,
-                stride, self._last_off, self.grad,
-                conv.w_off, conv.b_off, M, conv.out_dim,
-                conv.kernel_size, conv.in_dim,
             )
             return loss_buf if want_loss else None
         self.forward(xb, train_skip_logp=True)

@@ -15,7 +15,7 @@
 #define WAVE 64
 #define DEV_INLINE __device__ __forceinline__
 
-// activation tags (keep in sync with ops/functional.py ACT_IDS)
+// activation tags (keep in sync with ops/stacked.py ACT_IDS)
 enum ActKind : int {
   ACT_NONE = 0,
   ACT_RELU = 1,

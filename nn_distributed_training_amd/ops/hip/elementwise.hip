@@ -355,20 +355,6 @@ __global__ void gather_batch_dev_k(
   }
 }
 
-template <typename T>
-__global__ void gather_targets_dev_k(
-    const T* __restrict__ Y_all, const long* __restrict__ idx,
-    T* __restrict__ out, const long* __restrict__ offs_dev, int pit,
-    long maxlen, long B, long idx_stride, long total) {
-  const long idx_off = offs_dev[pit];
-  for (long t = blockIdx.x * (long)BLOCK + threadIdx.x; t < total;
-       t += (long)gridDim.x * BLOCK) {
-    const long l = t / B;
-    const long b = t - l * B;
-    out[t] = Y_all[l * maxlen + idx[l * idx_stride + idx_off + b]];
-  }
-}
-
 // Plain axpy: theta -= alpha * grad  (DSGD local step); zero_grad
 // clears grad after consuming it (next iteration's atomic kernels
 // then need no separate fill launch)

@@ -31,6 +31,25 @@ inline int grid_1d(long total, int block = 256, int cap = 4096) {
   AT_DISPATCH_FLOATING_TYPES(scalar_t_tensor.scalar_type(), "ndta_ops",    \
                              [&] { __VA_ARGS__ });
 
+// data pointer of an optional tensor; nullptr when it is absent
+template <typename T>
+inline T* opt_ptr(const c10::optional<torch::Tensor>& t) {
+  return t.has_value() ? t->data_ptr<T>() : nullptr;
+}
+
+// f(mode_c, pen_c): the optimizer mode (0 adam, 1 adamw, 2 sgd) and
+// the consensus-penalty flag as compile-time constants for the
+// fused_step*_k templates
+template <typename F>
+inline void dispatch_mode_pen(long mode, bool pen, F&& f) {
+  auto with_pen = [&](auto mode_c) {
+    pen ? f(mode_c, std::true_type{}) : f(mode_c, std::false_type{});
+  };
+  if (mode == 0) with_pen(std::integral_constant<int, 0>{});
+  else if (mode == 1) with_pen(std::integral_constant<int, 1>{});
+  else with_pen(std::integral_constant<int, 2>{});
+}
+
 // ---------------------------------------------------------------- ew --
 void dinno_dual_threg(torch::Tensor local,
                       c10::optional<torch::Tensor> remote,
@@ -43,7 +62,7 @@ void dinno_dual_threg(torch::Tensor local,
     hipLaunchKernelGGL(ew::dinno_dual_threg_k<scalar_t>,
         dim3(grid_1d(L * n)), dim3(ew::BLOCK), 0, cur_stream(),
         local.data_ptr<scalar_t>(),
-        remote.has_value() ? remote->data_ptr<scalar_t>() : nullptr,
+        opt_ptr<scalar_t>(remote),
         offs.data_ptr<int>(), idx.data_ptr<int>(),
         duals.data_ptr<scalar_t>(), s_out.data_ptr<scalar_t>(),
         (scalar_t)rho, n, L);
@@ -62,7 +81,7 @@ void mix_rows(torch::Tensor local, c10::optional<torch::Tensor> remote,
     hipLaunchKernelGGL(ew::mix_rows_k<scalar_t>,
         dim3(grid_1d(L * n)), dim3(ew::BLOCK), 0, cur_stream(),
         local.data_ptr<scalar_t>(),
-        remote.has_value() ? remote->data_ptr<scalar_t>() : nullptr,
+        opt_ptr<scalar_t>(remote),
         offs.data_ptr<int>(), idx.data_ptr<int>(),
         w.data_ptr<scalar_t>(), out.data_ptr<scalar_t>(), n, L);
   });
@@ -81,7 +100,7 @@ void dsgt_mix(torch::Tensor p_loc, torch::Tensor y_loc,
     hipLaunchKernelGGL(ew::dsgt_mix_k<scalar_t>,
         dim3(grid_1d(L * n)), dim3(ew::BLOCK), 0, cur_stream(),
         p_loc.data_ptr<scalar_t>(), y_loc.data_ptr<scalar_t>(),
-        remote.has_value() ? remote->data_ptr<scalar_t>() : nullptr,
+        opt_ptr<scalar_t>(remote),
         offs.data_ptr<int>(), idx.data_ptr<int>(),
         w.data_ptr<scalar_t>(), p_out.data_ptr<scalar_t>(),
         y_mix.data_ptr<scalar_t>(), (scalar_t)alpha, n, L);
@@ -112,19 +131,18 @@ void gather_targets(torch::Tensor Y_all, torch::Tensor idx,
   const long L = Y_all.size(0), maxlen = Y_all.size(1);
   const long B = out.numel() / L;
   const long total = out.numel();
-  if (Y_all.scalar_type() == torch::kLong) {
-    hipLaunchKernelGGL(ew::gather_targets_k<long>,
+  // targets are long labels or floating densities
+  auto launch = [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(ew::gather_targets_k<T>,
         dim3(grid_1d(total)), dim3(ew::BLOCK), 0, cur_stream(),
-        Y_all.data_ptr<long>(), idx.data_ptr<long>(),
-        out.data_ptr<long>(), maxlen, B, idx_stride, idx_off, total);
+        Y_all.data_ptr<T>(), idx.data_ptr<long>(), out.data_ptr<T>(),
+        maxlen, B, idx_stride, idx_off, total);
+  };
+  if (Y_all.scalar_type() == torch::kLong) {
+    launch(long{});
   } else {
-    DISPATCH_FT(Y_all, {
-      hipLaunchKernelGGL(ew::gather_targets_k<scalar_t>,
-          dim3(grid_1d(total)), dim3(ew::BLOCK), 0, cur_stream(),
-          Y_all.data_ptr<scalar_t>(), idx.data_ptr<long>(),
-          out.data_ptr<scalar_t>(), maxlen, B, idx_stride, idx_off,
-          total);
-    });
+    DISPATCH_FT(Y_all, { launch(scalar_t{}); });
   }
   HIP_CHECK_LAST();
 }
@@ -154,35 +172,24 @@ void fused_step(torch::Tensor theta, torch::Tensor grad,
   CHECK_DEV(theta); CHECK_DEV(grad);
   const long L = theta.size(0), n = theta.size(1);
   TORCH_CHECK(grad.numel() == L * nparts * n, "grad/nparts mismatch");
-  const bool pen = dual.has_value();
   DISPATCH_FT(theta, {
     const scalar_t bc1 =
         (scalar_t)(1.0 - std::pow(beta1, (double)step_t));
     const scalar_t bc2 =
         (scalar_t)(1.0 - std::pow(beta2, (double)step_t));
-    auto launch = [&](auto mode_c, auto pen_c) {
+    dispatch_mode_pen(mode, dual.has_value(), [&](auto mode_c,
+                                                  auto pen_c) {
       hipLaunchKernelGGL(
           (ew::fused_step_k<scalar_t, decltype(mode_c)::value,
                             decltype(pen_c)::value>),
           dim3(grid_1d(L * n)), dim3(ew::BLOCK), 0, cur_stream(),
           theta.data_ptr<scalar_t>(), grad.data_ptr<scalar_t>(),
-          pen ? dual->data_ptr<scalar_t>() : nullptr,
-          pen ? s->data_ptr<scalar_t>() : nullptr,
-          pen ? deg->data_ptr<int>() : nullptr,
-          m.has_value() ? m->data_ptr<scalar_t>() : nullptr,
-          v.has_value() ? v->data_ptr<scalar_t>() : nullptr,
+          opt_ptr<scalar_t>(dual), opt_ptr<scalar_t>(s),
+          opt_ptr<int>(deg), opt_ptr<scalar_t>(m), opt_ptr<scalar_t>(v),
           (scalar_t)rho, (scalar_t)lr, (scalar_t)beta1,
           (scalar_t)beta2, (scalar_t)eps, (scalar_t)wd, bc1, bc2,
           first_step ? 1 : 0, (int)nparts, n, L, zero_grad ? 1 : 0);
-    };
-    using c0 = std::integral_constant<int, 0>;
-    using c1 = std::integral_constant<int, 1>;
-    using c2 = std::integral_constant<int, 2>;
-    using bt = std::integral_constant<bool, true>;
-    using bf = std::integral_constant<bool, false>;
-    if (mode == 0) { pen ? launch(c0{}, bt{}) : launch(c0{}, bf{}); }
-    else if (mode == 1) { pen ? launch(c1{}, bt{}) : launch(c1{}, bf{}); }
-    else { pen ? launch(c2{}, bt{}) : launch(c2{}, bf{}); }
+    });
   });
   HIP_CHECK_LAST();
 }
@@ -198,7 +205,7 @@ void dinno_dual_threg_sched(torch::Tensor local,
     hipLaunchKernelGGL(ew::dinno_dual_threg_sched_k<scalar_t>,
         dim3(grid_1d(L * n)), dim3(ew::BLOCK), 0, cur_stream(),
         local.data_ptr<scalar_t>(),
-        remote.has_value() ? remote->data_ptr<scalar_t>() : nullptr,
+        opt_ptr<scalar_t>(remote),
         offs.data_ptr<int>(), idx.data_ptr<int>(),
         duals.data_ptr<scalar_t>(), s_out.data_ptr<scalar_t>(),
         sched.data_ptr<scalar_t>(), n, L);
@@ -218,31 +225,20 @@ void fused_step_sched(torch::Tensor theta, torch::Tensor grad,
   CHECK_DEV(theta); CHECK_DEV(grad);
   const long L = theta.size(0), n = theta.size(1);
   TORCH_CHECK(grad.numel() == L * nparts * n, "grad/nparts mismatch");
-  const bool pen = dual.has_value();
   DISPATCH_FT(theta, {
-    auto launch = [&](auto mode_c, auto pen_c) {
+    dispatch_mode_pen(mode, dual.has_value(), [&](auto mode_c,
+                                                  auto pen_c) {
       hipLaunchKernelGGL(
           (ew::fused_step_sched_k<scalar_t, decltype(mode_c)::value,
                                   decltype(pen_c)::value>),
           dim3(grid_1d(L * n)), dim3(ew::BLOCK), 0, cur_stream(),
           theta.data_ptr<scalar_t>(), grad.data_ptr<scalar_t>(),
-          pen ? dual->data_ptr<scalar_t>() : nullptr,
-          pen ? s->data_ptr<scalar_t>() : nullptr,
-          pen ? deg->data_ptr<int>() : nullptr,
-          m.has_value() ? m->data_ptr<scalar_t>() : nullptr,
-          v.has_value() ? v->data_ptr<scalar_t>() : nullptr,
+          opt_ptr<scalar_t>(dual), opt_ptr<scalar_t>(s),
+          opt_ptr<int>(deg), opt_ptr<scalar_t>(m), opt_ptr<scalar_t>(v),
           sched.data_ptr<scalar_t>(), (int)pit,
           (scalar_t)beta1, (scalar_t)beta2, (scalar_t)eps,
           (scalar_t)wd, first_step ? 1 : 0, (int)nparts, n, L);
-    };
-    using c0 = std::integral_constant<int, 0>;
-    using c1 = std::integral_constant<int, 1>;
-    using c2 = std::integral_constant<int, 2>;
-    using bt = std::integral_constant<bool, true>;
-    using bf = std::integral_constant<bool, false>;
-    if (mode == 0) { pen ? launch(c0{}, bt{}) : launch(c0{}, bf{}); }
-    else if (mode == 1) { pen ? launch(c1{}, bt{}) : launch(c1{}, bf{}); }
-    else { pen ? launch(c2{}, bt{}) : launch(c2{}, bf{}); }
+    });
   });
   HIP_CHECK_LAST();
 }
@@ -262,31 +258,6 @@ void gather_batch_dev(torch::Tensor X_all, torch::Tensor idx,
         out.data_ptr<scalar_t>(), offs_dev.data_ptr<long>(), (int)pit,
         maxlen, Fdim, B, idx_stride, total);
   });
-  HIP_CHECK_LAST();
-}
-
-void gather_targets_dev(torch::Tensor Y_all, torch::Tensor idx,
-                        torch::Tensor out, torch::Tensor offs_dev,
-                        long pit, long idx_stride) {
-  CHECK_DEV(Y_all); CHECK_DEV(out);
-  const long L = Y_all.size(0), maxlen = Y_all.size(1);
-  const long B = out.numel() / L;
-  const long total = out.numel();
-  if (Y_all.scalar_type() == torch::kLong) {
-    hipLaunchKernelGGL(ew::gather_targets_dev_k<long>,
-        dim3(grid_1d(total)), dim3(ew::BLOCK), 0, cur_stream(),
-        Y_all.data_ptr<long>(), idx.data_ptr<long>(),
-        out.data_ptr<long>(), offs_dev.data_ptr<long>(), (int)pit,
-        maxlen, B, idx_stride, total);
-  } else {
-    DISPATCH_FT(Y_all, {
-      hipLaunchKernelGGL(ew::gather_targets_dev_k<scalar_t>,
-          dim3(grid_1d(total)), dim3(ew::BLOCK), 0, cur_stream(),
-          Y_all.data_ptr<scalar_t>(), idx.data_ptr<long>(),
-          out.data_ptr<scalar_t>(), offs_dev.data_ptr<long>(),
-          (int)pit, maxlen, B, idx_stride, total);
-    });
-  }
   HIP_CHECK_LAST();
 }
 
@@ -327,7 +298,7 @@ void linear_fwd(torch::Tensor X, torch::Tensor theta, torch::Tensor Y,
   // I must be even for the 16-byte staging loads (vec2 alignment).
   const bool use_mfma = (M >= 128 && O >= 16 && I >= 8 && I % 2 == 0);
   DISPATCH_FT(X, {
-    auto zp = Z.has_value() ? Z->data_ptr<scalar_t>() : nullptr;
+    auto zp = opt_ptr<scalar_t>(Z);
     if (use_mfma) {
       dim3 grid((O + 63) / 64, (M + 63) / 64, L);
       hipLaunchKernelGGL(gmfma::mfma_fwd_k<scalar_t>,
@@ -383,8 +354,8 @@ void act_grad(torch::Tensor dY, torch::Tensor Y,
     hipLaunchKernelGGL(gemm::act_grad_k<scalar_t>,
         dim3(grid_1d(dY.numel())), dim3(256), 0, cur_stream(),
         dY.data_ptr<scalar_t>(), Y.data_ptr<scalar_t>(),
-        Z.has_value() ? Z->data_ptr<scalar_t>() : nullptr,
-        dZ.data_ptr<scalar_t>(), dY.numel(), (int)act, (scalar_t)scale);
+        opt_ptr<scalar_t>(Z), dZ.data_ptr<scalar_t>(), dY.numel(),
+        (int)act, (scalar_t)scale);
   });
   HIP_CHECK_LAST();
 }
@@ -405,9 +376,9 @@ void linear_bwd_dx(torch::Tensor dZ, torch::Tensor theta,
   const bool use_mfma =
       (M >= 128 && I >= 16 && O >= 8 && I % 2 == 0 && O % 2 == 0);
   DISPATCH_FT(dZ, {
-    auto ybp = Yb.has_value() ? Yb->data_ptr<scalar_t>() : nullptr;
-    auto zbp = Zb.has_value() ? Zb->data_ptr<scalar_t>() : nullptr;
-    auto xb2p = Xb2.has_value() ? Xb2->data_ptr<scalar_t>() : nullptr;
+    auto ybp = opt_ptr<scalar_t>(Yb);
+    auto zbp = opt_ptr<scalar_t>(Zb);
+    auto xb2p = opt_ptr<scalar_t>(Xb2);
     TORCH_CHECK(act_below == 0 || ybp != nullptr,
                 "act_below needs Yb");
     TORCH_CHECK(xb2p == nullptr || Ib <= 4,
@@ -445,16 +416,40 @@ void linear_bwd_dx(torch::Tensor dZ, torch::Tensor theta,
   HIP_CHECK_LAST();
 }
 
-// dW/db. PRECONDITION for the atomic paths (MFMA and small-chunked):
-// the layer's slice of gstack is zeroed (the stacked engine zeroes the
-// whole grad stack at backward start). The plain VALU path overwrites.
+// Which dW/db kernel a [M, I] x [M, O] layer shape gets. This is the
+// only place the thresholds are written: linear_bwd_dw switches on it,
+// dw_conv_bwd_idx merges launches where it is Small, and the stacked
+// engine asks dw_accumulates() which layers need a zeroed grad slice.
+enum class DwKernel { Direct, Mfma, SkinnyI, SkinnyO, SmallChunked, Small };
+
+inline DwKernel dw_kernel_for(long M, long I, long O) {
+  if (M >= 256 && O % 64 == 0 && I % 16 == 0 && I <= 448 && O <= 512) {
+    return DwKernel::Direct;
+  }
+  if (M >= 256 && I >= 16 && O >= 16) return DwKernel::Mfma;
+  if (M > 2048 && I <= 4 && O <= 256) return DwKernel::SkinnyI;
+  if (M > 2048 && O <= 4 && I <= 256) return DwKernel::SkinnyO;
+  if (M > 2048) return DwKernel::SmallChunked;
+  return DwKernel::Small;
+}
+
+// true where linear_bwd_dw ADDS into gstack, so the layer's slice must
+// be zero on entry; the Small 16x16-tile store-path kernel overwrites
+bool dw_accumulates(long M, long I, long O) {
+  return dw_kernel_for(M, I, O) != DwKernel::Small;
+}
+
+// dW/db. PRECONDITION where dw_accumulates(M, I, O): the layer's slice
+// of gstack is zeroed (the stacked engine zeroes the whole grad stack
+// at backward start).
 void linear_bwd_dw(torch::Tensor dZ, torch::Tensor X,
                    torch::Tensor gstack, long w_off, long b_off,
                    long M, long I, long O) {
   CHECK_DEV(dZ); CHECK_DEV(X); CHECK_DEV(gstack);
   const long L = gstack.size(0), n = gstack.size(1);
   DISPATCH_FT(dZ, {
-    if (M >= 256 && O % 64 == 0 && I % 16 == 0 && I <= 448 && O <= 512) {
+    switch (dw_kernel_for(M, I, O)) {
+    case DwKernel::Direct: {
       // full-I tiles: dZ and X each fetched from HBM exactly once;
       // direct-global fragment reads (both operands m-row-major), no
       // LDS/barriers — see gemm_mfma.hip mfma_dw_direct_k rationale.
@@ -475,26 +470,18 @@ void linear_bwd_dw(torch::Tensor dZ, torch::Tensor X,
         parts = torch::empty({L * nchunk * O * I}, gstack.options());
         pp = parts.data_ptr<scalar_t>();
       }
-      if (I <= 64) {
-        // fi_per == 1: NIMAX=1 keeps the load loops guard-free
-        hipLaunchKernelGGL((gmfma::mfma_dw_direct_k<scalar_t, 1>),
+      auto launch_direct = [&](auto nimax) {
+        hipLaunchKernelGGL(
+            (gmfma::mfma_dw_direct_k<scalar_t, decltype(nimax)::value>),
             grid, dim3(512), 0, cur_stream(),
             dZ.data_ptr<scalar_t>(), X.data_ptr<scalar_t>(),
             gstack.data_ptr<scalar_t>(), pp, n, w_off, b_off,
             (int)M, (int)I, (int)O, (int)nchunk);
-      } else if (I <= 256) {
-        hipLaunchKernelGGL((gmfma::mfma_dw_direct_k<scalar_t, 4>),
-            grid, dim3(512), 0, cur_stream(),
-            dZ.data_ptr<scalar_t>(), X.data_ptr<scalar_t>(),
-            gstack.data_ptr<scalar_t>(), pp, n, w_off, b_off,
-            (int)M, (int)I, (int)O, (int)nchunk);
-      } else {
-        hipLaunchKernelGGL((gmfma::mfma_dw_direct_k<scalar_t, 7>),
-            grid, dim3(512), 0, cur_stream(),
-            dZ.data_ptr<scalar_t>(), X.data_ptr<scalar_t>(),
-            gstack.data_ptr<scalar_t>(), pp, n, w_off, b_off,
-            (int)M, (int)I, (int)O, (int)nchunk);
-      }
+      };
+      // fi_per == 1: NIMAX=1 keeps the load loops guard-free
+      if (I <= 64) launch_direct(std::integral_constant<int, 1>{});
+      else if (I <= 256) launch_direct(std::integral_constant<int, 4>{});
+      else launch_direct(std::integral_constant<int, 7>{});
       if (pp != nullptr) {
         const long tile = O * I;
         dim3 rgrid(grid_1d(tile), 1, L);
@@ -503,7 +490,9 @@ void linear_bwd_dw(torch::Tensor dZ, torch::Tensor X,
             pp, gstack.data_ptr<scalar_t>(), n, w_off, tile,
             (int)nchunk);
       }
-    } else if (M >= 256 && I >= 16 && O >= 16) {
+      break;
+    }
+    case DwKernel::Mfma: {
       // fill the chip: tiles * L * nchunk ≈ 2048 blocks
       const long tiles = ((I + 63) / 64) * ((O + 63) / 64);
       long nchunk = std::max<long>(1, 2048 / std::max<long>(1, tiles * L));
@@ -514,7 +503,9 @@ void linear_bwd_dw(torch::Tensor dZ, torch::Tensor X,
           dZ.data_ptr<scalar_t>(), X.data_ptr<scalar_t>(),
           gstack.data_ptr<scalar_t>(), n, w_off, b_off,
           (int)M, (int)I, (int)O, (int)nchunk);
-    } else if (M > 2048 && I <= 4 && O <= 256) {
+      break;
+    }
+    case DwKernel::SkinnyI: {
       long nchunk = std::max<long>(1, 1024 / std::max<long>(1, L));
       nchunk = std::min<long>(nchunk, (M + 255) / 256);
       if (I == 2 && O == 256) {  // FourierNet encode shape: all
@@ -531,7 +522,9 @@ void linear_bwd_dw(torch::Tensor dZ, torch::Tensor X,
             gstack.data_ptr<scalar_t>(), n, w_off, b_off,
             (int)M, (int)I, (int)O, (int)nchunk);
       }
-    } else if (M > 2048 && O <= 4 && I <= 256) {
+      break;
+    }
+    case DwKernel::SkinnyO: {
       long nchunk = std::max<long>(1, 1024 / std::max<long>(1, L));
       nchunk = std::min<long>(nchunk, (M + 255) / 256);
       hipLaunchKernelGGL((gemm::dw_skinny_o_k<scalar_t, 4>),
@@ -539,7 +532,9 @@ void linear_bwd_dw(torch::Tensor dZ, torch::Tensor X,
           dZ.data_ptr<scalar_t>(), X.data_ptr<scalar_t>(),
           gstack.data_ptr<scalar_t>(), n, w_off, b_off,
           (int)M, (int)I, (int)O, (int)nchunk);
-    } else if (M > 2048) {
+      break;
+    }
+    case DwKernel::SmallChunked: {
       const long total = O * I + O;
       long nchunk = std::max<long>(
           1, 2048 / std::max<long>(1, ((total + 255) / 256) * L));
@@ -550,77 +545,124 @@ void linear_bwd_dw(torch::Tensor dZ, torch::Tensor X,
           dZ.data_ptr<scalar_t>(), X.data_ptr<scalar_t>(),
           gstack.data_ptr<scalar_t>(), n, w_off, b_off,
           (int)M, (int)I, (int)O, (int)nchunk);
-    } else {
+      break;
+    }
+    case DwKernel::Small: {
       dim3 grid((I + 15) / 16, (O + 15) / 16, L);
       hipLaunchKernelGGL(gemm::linear_bwd_dw_k<scalar_t>,
           grid, dim3(16, 16), 0, cur_stream(),
           dZ.data_ptr<scalar_t>(), X.data_ptr<scalar_t>(),
           gstack.data_ptr<scalar_t>(), n, w_off, b_off,
           (int)M, (int)I, (int)O);
+      break;
+    }
     }
   });
   HIP_CHECK_LAST();
 }
 
 // -------------------------------------------------------------- conv --
-void conv_pool_fwd(torch::Tensor X, torch::Tensor theta, torch::Tensor Y,
-                   torch::Tensor idx, long w_off, long b_off, long B,
-                   long F, long K, long IMG) {
+// f(kmax_c): KMAX sizes the conv kernels' per-thread dW register
+// block; the K<=5 variant saves 48 VGPRs over the generic K<=7 one
+// (occupancy)
+template <typename Fn>
+inline void dispatch_kmax(long K, Fn&& f) {
+  if (K <= 5) f(std::integral_constant<int, 5>{});
+  else f(std::integral_constant<int, 7>{});
+}
+
+// conv backward splits each (node, filter)'s batch into this many
+// chunks, one block each
+inline int conv_bwd_nchunk(long B) { return (int)std::min<long>(B, 32); }
+
+// The launchers take the image source as (src_idx, idx_stride, idx_off,
+// maxlen): X is the resident dataset [L, maxlen, IMG*IMG] read through
+// the sampler's index stream (no gather_batch launch, no xb buffer
+// round-trip); nullptr, 0, 0, 0 means X is the batch itself.
+void launch_conv_fwd(const torch::Tensor& X, const torch::Tensor& theta,
+                     const torch::Tensor& Y, const torch::Tensor& idx,
+                     long w_off, long b_off, long B, long F, long K,
+                     long IMG,
+                     const long* src_idx, long idx_stride, long idx_off,
+                     long maxlen) {
   CHECK_DEV(X); CHECK_DEV(theta); CHECK_DEV(Y);
   const long L = theta.size(0), n = theta.size(1);
   TORCH_CHECK(K <= 7, "conv_pool_fwd supports kernel size <= 7");
   DISPATCH_FT(X, {
     const size_t shmem =
         (IMG * IMG + F * K * K + F) * sizeof(scalar_t);
-    if (K <= 5) {
-      hipLaunchKernelGGL((conv::conv_pool_fwd_k<scalar_t, 5>),
+    dispatch_kmax(K, [&](auto kmax) {
+      hipLaunchKernelGGL(
+          (conv::conv_pool_fwd_k<scalar_t, decltype(kmax)::value>),
           dim3(L * B), dim3(256), shmem, cur_stream(),
           X.data_ptr<scalar_t>(), theta.data_ptr<scalar_t>(),
           Y.data_ptr<scalar_t>(), idx.data_ptr<unsigned char>(),
           n, w_off, b_off, (int)B, (int)F, (int)K, (int)IMG,
-          (const long*)nullptr, 0L, 0L, 0L);
-    } else {
-      hipLaunchKernelGGL((conv::conv_pool_fwd_k<scalar_t, 7>),
-          dim3(L * B), dim3(256), shmem, cur_stream(),
-          X.data_ptr<scalar_t>(), theta.data_ptr<scalar_t>(),
-          Y.data_ptr<scalar_t>(), idx.data_ptr<unsigned char>(),
-          n, w_off, b_off, (int)B, (int)F, (int)K, (int)IMG,
-          (const long*)nullptr, 0L, 0L, 0L);
-    }
+          src_idx, idx_stride, idx_off, maxlen);
+    });
   });
   HIP_CHECK_LAST();
 }
 
-void conv_pool_bwd(torch::Tensor dY, torch::Tensor idx, torch::Tensor X,
-                   torch::Tensor gstack, long w_off, long b_off, long B,
-                   long F, long K, long IMG) {
+void launch_conv_bwd(const torch::Tensor& dY, const torch::Tensor& idx,
+                     const torch::Tensor& X, const torch::Tensor& gstack,
+                     long w_off, long b_off, long B, long F, long K,
+                     long IMG,
+                     const long* src_idx, long idx_stride, long idx_off,
+                     long maxlen) {
   CHECK_DEV(dY); CHECK_DEV(X); CHECK_DEV(gstack);
   const long L = gstack.size(0), n = gstack.size(1);
   TORCH_CHECK(K <= 7, "conv_pool_bwd supports kernel size <= 7");
   // batch-chunked (l, f, chunk) grid with block-tree reduction +
   // atomics; measured best of three structures on the MNIST bench
   // (LDS-staged image variant was 2x slower — profiles/README.md)
-  const int nchunk = (int)std::min<long>(B, 32);
+  const int nchunk = conv_bwd_nchunk(B);
   DISPATCH_FT(dY, {
-    // KMAX sizes the per-thread dW register block: the K<=5 variant
-    // saves 48 VGPRs over the generic K<=7 one (occupancy)
-    if (K <= 5) {
-      hipLaunchKernelGGL((conv::conv_pool_bwd_k<scalar_t, 5>),
+    dispatch_kmax(K, [&](auto kmax) {
+      hipLaunchKernelGGL(
+          (conv::conv_pool_bwd_k<scalar_t, decltype(kmax)::value>),
           dim3(L * F * nchunk), dim3(256), 0, cur_stream(),
           dY.data_ptr<scalar_t>(), idx.data_ptr<unsigned char>(),
           X.data_ptr<scalar_t>(), gstack.data_ptr<scalar_t>(),
           n, w_off, b_off, (int)B, (int)F, (int)K, (int)IMG, nchunk,
-          (const long*)nullptr, 0L, 0L, 0L);
-    } else {
-      hipLaunchKernelGGL((conv::conv_pool_bwd_k<scalar_t, 7>),
-          dim3(L * F * nchunk), dim3(256), 0, cur_stream(),
-          dY.data_ptr<scalar_t>(), idx.data_ptr<unsigned char>(),
-          X.data_ptr<scalar_t>(), gstack.data_ptr<scalar_t>(),
-          n, w_off, b_off, (int)B, (int)F, (int)K, (int)IMG, nchunk,
-          (const long*)nullptr, 0L, 0L, 0L);
-    }
+          src_idx, idx_stride, idx_off, maxlen);
+    });
   });
   HIP_CHECK_LAST();
+}
+
+void conv_pool_fwd(torch::Tensor X, torch::Tensor theta, torch::Tensor Y,
+                   torch::Tensor idx, long w_off, long b_off, long B,
+                   long F, long K, long IMG) {
+  launch_conv_fwd(X, theta, Y, idx, w_off, b_off, B, F, K, IMG, nullptr,
+                  0, 0, 0);
+}
+
+void conv_pool_bwd(torch::Tensor dY, torch::Tensor idx, torch::Tensor X,
+                   torch::Tensor gstack, long w_off, long b_off, long B,
+                   long F, long K, long IMG) {
+  launch_conv_bwd(dY, idx, X, gstack, w_off, b_off, B, F, K, IMG,
+                  nullptr, 0, 0, 0);
+}
+
+void conv_pool_fwd_idx(torch::Tensor X_all, torch::Tensor src_idx,
+                       long idx_stride, long idx_off,
+                       torch::Tensor theta, torch::Tensor Y,
+                       torch::Tensor idx, long w_off, long b_off,
+                       long B, long F, long K, long IMG) {
+  launch_conv_fwd(X_all, theta, Y, idx, w_off, b_off, B, F, K, IMG,
+                  src_idx.data_ptr<long>(), idx_stride, idx_off,
+                  X_all.size(1));
+}
+
+void conv_pool_bwd_idx(torch::Tensor dY, torch::Tensor idx,
+                       torch::Tensor X_all, torch::Tensor src_idx,
+                       long idx_stride, long idx_off,
+                       torch::Tensor gstack, long w_off, long b_off,
+                       long B, long F, long K, long IMG) {
+  launch_conv_bwd(dY, idx, X_all, gstack, w_off, b_off, B, F, K, IMG,
+                  src_idx.data_ptr<long>(), idx_stride, idx_off,
+                  X_all.size(1));
 }
 
 // ------------------------------------------------------------ losses --
@@ -658,9 +700,9 @@ void mnist_train_step(
         grid, dim3(256), shmem, cur_stream(),
         X_all.data_ptr<scalar_t>(), Y_all.data_ptr<long>(),
         idx.data_ptr<long>(),
-        offs_dev.has_value() ? offs_dev->data_ptr<long>() : nullptr,
+        opt_ptr<long>(offs_dev),
         theta.data_ptr<scalar_t>(), grad.data_ptr<scalar_t>(),
-        loss.has_value() ? loss->data_ptr<scalar_t>() : nullptr,
+        opt_ptr<scalar_t>(loss),
         (int)pit, idx_off, idx_stride, maxlen, n,
         wc_off, bc_off, w1_off, b1_off, w2_off, b2_off,
         (int)B, (int)F, (int)K, (int)IMG, (int)H, (int)C, (int)TI,
@@ -690,7 +732,7 @@ void nll_bwd(torch::Tensor logp, torch::Tensor y, torch::Tensor dZ,
         dim3(grid_1d(M)), dim3(256), 0, cur_stream(),
         logp.data_ptr<scalar_t>(), y.data_ptr<long>(),
         dZ.data_ptr<scalar_t>(),
-        loss.has_value() ? loss->data_ptr<scalar_t>() : nullptr,
+        opt_ptr<scalar_t>(loss),
         M, (int)C, (int)B, (scalar_t)loss_scale);
   });
   HIP_CHECK_LAST();
@@ -710,8 +752,8 @@ void nll_fused(torch::Tensor Z, torch::Tensor Y_all,
         dim3(grid_1d(M)), dim3(256), 0, cur_stream(),
         Z.data_ptr<scalar_t>(), Y_all.data_ptr<long>(),
         idx.data_ptr<long>(), dZ.data_ptr<scalar_t>(),
-        loss.has_value() ? loss->data_ptr<scalar_t>() : nullptr,
-        offs_dev.has_value() ? offs_dev->data_ptr<long>() : nullptr,
+        opt_ptr<scalar_t>(loss),
+        opt_ptr<long>(offs_dev),
         (int)pit, maxlen, idx_stride, idx_off, M, (int)C, (int)B,
         (scalar_t)loss_scale);
   });
@@ -727,7 +769,7 @@ void bce_bwd(torch::Tensor p, torch::Tensor tgt, torch::Tensor dZ,
         dim3(grid_1d(p.numel())), dim3(256), 0, cur_stream(),
         p.data_ptr<scalar_t>(), tgt.data_ptr<scalar_t>(),
         dZ.data_ptr<scalar_t>(),
-        loss.has_value() ? loss->data_ptr<scalar_t>() : nullptr,
+        opt_ptr<scalar_t>(loss),
         p.numel(), (int)B, (scalar_t)loss_scale);
   });
   HIP_CHECK_LAST();
@@ -738,98 +780,18 @@ void regression_bwd(torch::Tensor yhat, torch::Tensor tgt,
                     long B, double loss_scale, long mode) {
   CHECK_DEV(yhat); CHECK_DEV(dY);
   DISPATCH_FT(yhat, {
-    auto lptr =
-        loss.has_value() ? loss->data_ptr<scalar_t>() : nullptr;
-    if (mode == 0) {
-      hipLaunchKernelGGL((losses::regression_bwd_k<scalar_t, 0>),
+    auto launch = [&](auto mode_c) {
+      hipLaunchKernelGGL(
+          (losses::regression_bwd_k<scalar_t, decltype(mode_c)::value>),
           dim3(grid_1d(yhat.numel())), dim3(256), 0, cur_stream(),
           yhat.data_ptr<scalar_t>(), tgt.data_ptr<scalar_t>(),
-          dY.data_ptr<scalar_t>(), lptr, yhat.numel(), (int)B,
-          (scalar_t)loss_scale);
-    } else {
-      hipLaunchKernelGGL((losses::regression_bwd_k<scalar_t, 1>),
-          dim3(grid_1d(yhat.numel())), dim3(256), 0, cur_stream(),
-          yhat.data_ptr<scalar_t>(), tgt.data_ptr<scalar_t>(),
-          dY.data_ptr<scalar_t>(), lptr, yhat.numel(), (int)B,
-          (scalar_t)loss_scale);
-    }
+          dY.data_ptr<scalar_t>(), opt_ptr<scalar_t>(loss),
+          yhat.numel(), (int)B, (scalar_t)loss_scale);
+    };
+    if (mode == 0) launch(std::integral_constant<int, 0>{});
+    else launch(std::integral_constant<int, 1>{});
   });
   HIP_CHECK_LAST();
-}
-
-
-// gather-fused conv wrappers: image rows read straight from the
-// resident dataset via the sampler's index stream (no gather_batch
-// launch, no xb buffer round-trip)
-void conv_pool_fwd_idx(torch::Tensor X_all, torch::Tensor src_idx,
-                       long idx_stride, long idx_off,
-                       torch::Tensor theta, torch::Tensor Y,
-                       torch::Tensor idx, long w_off, long b_off,
-                       long B, long F, long K, long IMG) {
-  CHECK_DEV(X_all); CHECK_DEV(theta); CHECK_DEV(Y);
-  const long L = theta.size(0), n = theta.size(1);
-  const long maxlen = X_all.size(1);
-  TORCH_CHECK(K <= 7, "conv_pool_fwd supports kernel size <= 7");
-  DISPATCH_FT(X_all, {
-    const size_t shmem =
-        (IMG * IMG + F * K * K + F) * sizeof(scalar_t);
-    if (K <= 5) {
-      hipLaunchKernelGGL((conv::conv_pool_fwd_k<scalar_t, 5>),
-          dim3(L * B), dim3(256), shmem, cur_stream(),
-          X_all.data_ptr<scalar_t>(), theta.data_ptr<scalar_t>(),
-          Y.data_ptr<scalar_t>(), idx.data_ptr<unsigned char>(),
-          n, w_off, b_off, (int)B, (int)F, (int)K, (int)IMG,
-          src_idx.data_ptr<long>(), idx_stride, idx_off, maxlen);
-    } else {
-      hipLaunchKernelGGL((conv::conv_pool_fwd_k<scalar_t, 7>),
-          dim3(L * B), dim3(256), shmem, cur_stream(),
-          X_all.data_ptr<scalar_t>(), theta.data_ptr<scalar_t>(),
-          Y.data_ptr<scalar_t>(), idx.data_ptr<unsigned char>(),
-          n, w_off, b_off, (int)B, (int)F, (int)K, (int)IMG,
-          src_idx.data_ptr<long>(), idx_stride, idx_off, maxlen);
-    }
-  });
-  HIP_CHECK_LAST();
-}
-
-void conv_pool_bwd_idx(torch::Tensor dY, torch::Tensor idx,
-                       torch::Tensor X_all, torch::Tensor src_idx,
-                       long idx_stride, long idx_off,
-                       torch::Tensor gstack, long w_off, long b_off,
-                       long B, long F, long K, long IMG) {
-  CHECK_DEV(dY); CHECK_DEV(X_all); CHECK_DEV(gstack);
-  const long L = gstack.size(0), n = gstack.size(1);
-  const long maxlen = X_all.size(1);
-  TORCH_CHECK(K <= 7, "conv_pool_bwd supports kernel size <= 7");
-  const int nchunk = (int)std::min<long>(B, 32);
-  DISPATCH_FT(dY, {
-    if (K <= 5) {
-      hipLaunchKernelGGL((conv::conv_pool_bwd_k<scalar_t, 5>),
-          dim3(L * F * nchunk), dim3(256), 0, cur_stream(),
-          dY.data_ptr<scalar_t>(), idx.data_ptr<unsigned char>(),
-          X_all.data_ptr<scalar_t>(), gstack.data_ptr<scalar_t>(),
-          n, w_off, b_off, (int)B, (int)F, (int)K, (int)IMG, nchunk,
-          src_idx.data_ptr<long>(), idx_stride, idx_off, maxlen);
-    } else {
-      hipLaunchKernelGGL((conv::conv_pool_bwd_k<scalar_t, 7>),
-          dim3(L * F * nchunk), dim3(256), 0, cur_stream(),
-          dY.data_ptr<scalar_t>(), idx.data_ptr<unsigned char>(),
-          X_all.data_ptr<scalar_t>(), gstack.data_ptr<scalar_t>(),
-          n, w_off, b_off, (int)B, (int)F, (int)K, (int)IMG, nchunk,
-          src_idx.data_ptr<long>(), idx_stride, idx_off, maxlen);
-    }
-  });
-  HIP_CHECK_LAST();
-}
-
-// true where linear_bwd_dw() above ends in its last branch, the small
-// 16x16-tile store-path kernel (mirrors its branch conditions)
-inline bool dw_takes_small_kernel(long M, long I, long O) {
-  if (M >= 256 && O % 64 == 0 && I % 16 == 0 && I <= 448 && O <= 512) {
-    return false;
-  }
-  if (M >= 256 && I >= 16 && O >= 16) return false;
-  return M <= 2048;
 }
 
 // fc1 dW/db + gather-sourced conv dW/db in ONE launch (fused_mnist.hip
@@ -843,7 +805,7 @@ void dw_conv_bwd_idx(torch::Tensor dZ, torch::Tensor X,
                      torch::Tensor gstack, long w_off, long b_off,
                      long M, long I, long O, long cw_off, long cb_off,
                      long F, long K, long IMG) {
-  if (!dw_takes_small_kernel(M, I, O)) {
+  if (dw_kernel_for(M, I, O) != DwKernel::Small) {
     linear_bwd_dw(dZ, X, gstack, w_off, b_off, M, I, O);
     conv_pool_bwd_idx(dY, pidx, X_all, src_idx, idx_stride, idx_off,
                       gstack, cw_off, cb_off, M, F, K, IMG);
@@ -854,13 +816,14 @@ void dw_conv_bwd_idx(torch::Tensor dZ, torch::Tensor X,
   const long L = gstack.size(0), n = gstack.size(1);
   const long maxlen = X_all.size(1);
   TORCH_CHECK(K <= 7, "conv_pool_bwd supports kernel size <= 7");
-  const int nchunk = (int)std::min<long>(M, 32);
+  const int nchunk = conv_bwd_nchunk(M);
   const long gx = (I + 15) / 16, gy = (O + 15) / 16;
   const long n_dw = gx * gy * L;
   const long n_cv = L * F * nchunk;
   DISPATCH_FT(dZ, {
-    if (K <= 5) {
-      hipLaunchKernelGGL((fmnist::dw_conv_bwd_k<scalar_t, 5>),
+    dispatch_kmax(K, [&](auto kmax) {
+      hipLaunchKernelGGL(
+          (fmnist::dw_conv_bwd_k<scalar_t, decltype(kmax)::value>),
           dim3(n_dw + n_cv), dim3(256), 0, cur_stream(),
           dZ.data_ptr<scalar_t>(), X.data_ptr<scalar_t>(), w_off, b_off,
           (int)M, (int)I, (int)O, (int)gx, (int)gy, (int)n_dw,
@@ -868,16 +831,7 @@ void dw_conv_bwd_idx(torch::Tensor dZ, torch::Tensor X,
           X_all.data_ptr<scalar_t>(), cw_off, cb_off, (int)F, (int)K,
           (int)IMG, nchunk, src_idx.data_ptr<long>(), idx_stride,
           idx_off, maxlen, gstack.data_ptr<scalar_t>(), n);
-    } else {
-      hipLaunchKernelGGL((fmnist::dw_conv_bwd_k<scalar_t, 7>),
-          dim3(n_dw + n_cv), dim3(256), 0, cur_stream(),
-          dZ.data_ptr<scalar_t>(), X.data_ptr<scalar_t>(), w_off, b_off,
-          (int)M, (int)I, (int)O, (int)gx, (int)gy, (int)n_dw,
-          dY.data_ptr<scalar_t>(), pidx.data_ptr<unsigned char>(),
-          X_all.data_ptr<scalar_t>(), cw_off, cb_off, (int)F, (int)K,
-          (int)IMG, nchunk, src_idx.data_ptr<long>(), idx_stride,
-          idx_off, maxlen, gstack.data_ptr<scalar_t>(), n);
-    }
+    });
   });
   HIP_CHECK_LAST();
 }
@@ -904,7 +858,7 @@ void fc_block_launch(torch::Tensor x0, torch::Tensor theta,
         Y_all.data_ptr<long>(), idx.data_ptr<long>(), idx_stride,
         idx_off, maxlen, grad.data_ptr<scalar_t>(),
         dx0.data_ptr<scalar_t>(), dz1g.data_ptr<scalar_t>(),
-        loss.has_value() ? loss->data_ptr<scalar_t>() : nullptr,
+        opt_ptr<scalar_t>(loss),
         n, w1_off, b1_off, w2_off, b2_off, (int)M, (int)I, (int)H,
         (int)C, (scalar_t)loss_scale, mask_dx0 ? 1 : 0);
   });
@@ -1010,7 +964,13 @@ std::vector<torch::Tensor> consensus_cdist(torch::Tensor stack) {
 // spec: CPU int64 [nl, 7] rows = (kind, w_off, b_off, in_dim,
 //       out_dim, act, ksize); kind 0 = linear, 1 = conv_pool;
 //       act = ACT_* id (5 = logsoftmax -> linear 'none' + row kernel).
+//       Written by StackedEngine._chain_meta() in ops/stacked.py.
 // scales: CPU float64 [nl] activation scales.
+enum SpecCol {
+  SP_KIND, SP_W_OFF, SP_B_OFF, SP_IN_DIM, SP_OUT_DIM, SP_ACT, SP_KSIZE,
+  SP_NCOLS
+};
+
 void fwd_chain(torch::Tensor spec, torch::Tensor scales,
                c10::optional<torch::Tensor> X_all,
                c10::optional<torch::Tensor> idx, long idx_stride,
@@ -1021,8 +981,9 @@ void fwd_chain(torch::Tensor spec, torch::Tensor scales,
                std::vector<c10::optional<torch::Tensor>> idxs,
                c10::optional<torch::Tensor> logp, long M,
                bool train_skip_logp) {
-  TORCH_CHECK(spec.device().is_cpu() && scales.device().is_cpu(),
-              "spec/scales must be CPU tensors");
+  TORCH_CHECK(spec.device().is_cpu() && scales.device().is_cpu() &&
+                  spec.size(1) == SP_NCOLS,
+              "spec [nl, 7] / scales must be CPU tensors");
   const auto sp = spec.accessor<long, 2>();
   const auto sc = scales.accessor<double, 1>();
   const long nl = spec.size(0);
@@ -1031,9 +992,10 @@ void fwd_chain(torch::Tensor spec, torch::Tensor scales,
   }
   torch::Tensor cur = xb;
   for (long li = 0; li < nl; ++li) {
-    const long kind = sp[li][0], w_off = sp[li][1], b_off = sp[li][2];
-    const long in_dim = sp[li][3], out_dim = sp[li][4];
-    const long act = sp[li][5], ksize = sp[li][6];
+    const long kind = sp[li][SP_KIND], w_off = sp[li][SP_W_OFF],
+               b_off = sp[li][SP_B_OFF], in_dim = sp[li][SP_IN_DIM],
+               out_dim = sp[li][SP_OUT_DIM], act = sp[li][SP_ACT],
+               ksize = sp[li][SP_KSIZE];
     torch::Tensor out = acts[li];
     if (kind == 1) {
       conv_pool_fwd(cur, theta, out, *idxs[li], w_off, b_off, M,
@@ -1075,8 +1037,9 @@ void bwd_chain(torch::Tensor spec, torch::Tensor scales,
                c10::optional<torch::Tensor> yb,
                c10::optional<torch::Tensor> loss, double loss_scale,
                long M, long zero_mode) {
-  TORCH_CHECK(spec.device().is_cpu() && scales.device().is_cpu(),
-              "spec/scales must be CPU tensors");
+  TORCH_CHECK(spec.device().is_cpu() && scales.device().is_cpu() &&
+                  spec.size(1) == SP_NCOLS,
+              "spec [nl, 7] / scales must be CPU tensors");
   const auto sp = spec.accessor<long, 2>();
   const auto sc = scales.accessor<double, 1>();
   const long nl = spec.size(0);
@@ -1085,12 +1048,11 @@ void bwd_chain(torch::Tensor spec, torch::Tensor scales,
   } else if (zero_mode == 2) {
     // conv slices only (kind == 1 rows)
     for (long li = 0; li < nl; ++li) {
-      if (sp[li][0] == 1) {
-        const long cnt =
-            sp[li][4] * sp[li][6] * sp[li][6] + sp[li][4];
+      if (sp[li][SP_KIND] == 1) {
+        const long F = sp[li][SP_OUT_DIM], K = sp[li][SP_KSIZE];
+        const long w_off = sp[li][SP_W_OFF];
         grad.index({torch::indexing::Slice(),
-                    torch::indexing::Slice(sp[li][1],
-                                           sp[li][1] + cnt)})
+                    torch::indexing::Slice(w_off, w_off + F * K * K + F)})
             .zero_();
       }
     }
@@ -1101,29 +1063,31 @@ void bwd_chain(torch::Tensor spec, torch::Tensor scales,
   torch::Tensor dz = dzs[last];
   if (loss_kind == 0) {
     nll_fused(acts[last], *Y_all, *idx, dz, loss, graph_offs, pit,
-              idx_stride, idx_off, sp[last][4], M, loss_scale);
+              idx_stride, idx_off, sp[last][SP_OUT_DIM], M, loss_scale);
   } else if (loss_kind == 1) {
     bce_bwd(acts[last], *yb, dz, loss, M, loss_scale);
   } else {
     auto dy = torch::empty_like(dz);
     regression_bwd(acts[last], *yb, dy, loss, M, loss_scale,
                    loss_kind == 2 ? 0 : 1);
-    act_grad(dy, acts[last], c10::nullopt, dz, sp[last][5], sc[last]);
+    act_grad(dy, acts[last], c10::nullopt, dz, sp[last][SP_ACT],
+             sc[last]);
   }
 
   for (long li = last; li >= 0; --li) {
-    const long kind = sp[li][0], w_off = sp[li][1], b_off = sp[li][2];
-    const long in_dim = sp[li][3], out_dim = sp[li][4];
+    const long kind = sp[li][SP_KIND], w_off = sp[li][SP_W_OFF],
+               b_off = sp[li][SP_B_OFF], in_dim = sp[li][SP_IN_DIM],
+               out_dim = sp[li][SP_OUT_DIM];
     torch::Tensor below = li > 0 ? acts[li - 1] : xb;
     dz = dzs[li];
     if (kind == 1) {
       conv_pool_bwd(dz, *idxs[li], below, grad, w_off, b_off, M,
-                    out_dim, sp[li][6], in_dim);
+                    out_dim, sp[li][SP_KSIZE], in_dim);
       continue;  // conv is the first layer: no dX
     }
     linear_bwd_dw(dz, below, grad, w_off, b_off, M, in_dim, out_dim);
     if (li > 0) {
-      const long act_b_raw = sp[li - 1][5];
+      const long act_b_raw = sp[li - 1][SP_ACT];
       const long act_b =
           (act_b_raw == ACT_NONE || act_b_raw == ACT_LOGSOFTMAX)
               ? 0 : act_b_raw;
@@ -1131,9 +1095,9 @@ void bwd_chain(torch::Tensor spec, torch::Tensor scales,
       long wb_off = 0, bb_off = 0, ib = 0;
       if (act_b == ACT_SIN_RELU && !zs[li - 1].has_value()) {
         xb2 = li - 1 > 0 ? acts[li - 2] : xb;
-        wb_off = sp[li - 1][1];
-        bb_off = sp[li - 1][2];
-        ib = sp[li - 1][3];
+        wb_off = sp[li - 1][SP_W_OFF];
+        bb_off = sp[li - 1][SP_B_OFF];
+        ib = sp[li - 1][SP_IN_DIM];
       }
       linear_bwd_dx(
           dz, theta, dzs[li - 1],
@@ -1175,7 +1139,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("reduce_parts", &reduce_parts);
   mod.def("gather_batch", &gather_batch);
   mod.def("gather_batch_dev", &gather_batch_dev);
-  mod.def("gather_targets_dev", &gather_targets_dev);
   mod.def("dinno_dual_threg_sched", &dinno_dual_threg_sched);
   mod.def("fused_step_sched", &fused_step_sched);
   mod.def("gather_targets", &gather_targets);
@@ -1183,6 +1146,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("act_grad", &act_grad);
   mod.def("linear_bwd_dx", &linear_bwd_dx);
   mod.def("linear_bwd_dw", &linear_bwd_dw);
+  mod.def("dw_accumulates", &dw_accumulates);
   mod.def("conv_pool_fwd", &conv_pool_fwd);
   mod.def("conv_pool_bwd", &conv_pool_bwd);
   mod.def("conv_pool_fwd_idx", &conv_pool_fwd_idx);

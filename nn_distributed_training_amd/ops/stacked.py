@@ -183,6 +183,11 @@ class _StreamSampler:
         off = self.next_offset()
         return self.stream, self.S, off
 
+    def index_ref(self):
+        """(index tensor, row stride) the kernels that gather through
+        the index stream read the current batch from."""
+        return self.stream, self.S
+
 
 class _OnlineWindowSampler:
     """Sliding-window sampler mirroring OnlineTrajectoryLidarDataset:
@@ -297,6 +302,9 @@ class _OnlineWindowSampler:
                 )
                 self.pos[li] = take
         return self.buf, self.B, 0
+
+    def index_ref(self):
+        return self.buf, self.B
 
 
 class StackedEngine:
@@ -641,10 +649,7 @@ class StackedEngine:
             conv, fc1, fc2 = self.spec.layers
             M = self.B
             ext = self.ext
-            idx_t = self.sampler.stream if hasattr(
-                self.sampler, "stream") else self.sampler.buf
-            stride = self.sampler.S if hasattr(
-                self.sampler, "S") else self.B
+            idx_t, stride = self.sampler.index_ref()
             # fc grads accumulate atomically: the stack must be all
             # zeros here. The step kernels clear it as they consume it
             # (zero_grad), so the fill launch is usually skipped.
@@ -672,6 +677,31 @@ class StackedEngine:
             graph_offs=graph_offs, pit=pit,
         )
 
+    def train_step(self, want_loss=False):
+        """Draw the next batch and run forward + backward on it, by the
+        megakernel where it is enabled, else by the layered path.
+        Returns (loss or None, grad tensor, nparts): the megakernel
+        leaves [L, nparts, n] per-tile slabs, the layered path
+        self.grad with nparts 1."""
+        if self.fused_step_available():
+            with _timer("train_step"):
+                lb = self.run_fused_mnist(
+                    off=self.fused_advance(), want_loss=want_loss
+                )
+            return lb, self.grad_parts, self.fused_nparts
+        with _timer("next_batch"):
+            xb, yb = self.next_batch()
+        with _timer("fwd_bwd"):
+            lb = self.fwd_bwd(xb, yb, want_loss=want_loss)
+        return lb, self.grad, 1
+
+    def train_step_reduced(self, want_loss=False):
+        """train_step() with the gradient left in self.grad."""
+        lb, grad_t, _ = self.train_step(want_loss)
+        if grad_t is not self.grad:
+            self.reduce_fused_grad()
+        return lb
+
     # ------------------------------------------------------------------
     def backward(self, xb, yb, loss_scale=1.0, want_loss=False,
                  graph_offs=None, pit=0):
@@ -682,8 +712,9 @@ class StackedEngine:
         M = self.B
         # atomic-accumulating layers need their grad slices zeroed;
         # store-path layers overwrite. Zero the whole stack only when a
-        # big atomic linear layer exists (density), else just the conv
-        # slices (MNIST: 78 of 28440 elements).
+        # linear layer's dW kernel accumulates (density; the kernel
+        # choice is ext.hip dw_kernel_for), else just the conv slices
+        # (MNIST: 78 of 28440 elements).
         if self._zero_plan is None:
             slices = []
             whole = False
@@ -692,8 +723,7 @@ class StackedEngine:
                     cnt = (layer.out_dim * layer.kernel_size**2
                            + layer.out_dim)
                     slices.append((layer.w_off, cnt))
-                elif (M >= 256 and layer.in_dim >= 16
-                      and layer.out_dim >= 16) or M > 2048:
+                elif ext.dw_accumulates(M, layer.in_dim, layer.out_dim):
                     whole = True
             self._zero_plan = ("whole",) if whole else ("slices", slices)
         if self._use_chain:
@@ -701,15 +731,7 @@ class StackedEngine:
             loss_buf = bufs["loss"] if want_loss else None
             last = layers[-1]
             if self.classification:
-                idx_t = (
-                    self.sampler.stream
-                    if hasattr(self.sampler, "stream")
-                    else self.sampler.buf
-                )
-                stride = (
-                    self.sampler.S
-                    if hasattr(self.sampler, "S") else self.B
-                )
+                idx_t, stride = self.sampler.index_ref()
                 loss_kind = 0
                 yb_arg = None
                 idx_off = 0 if graph_offs is not None else self._last_off
@@ -747,14 +769,7 @@ class StackedEngine:
         dz = bufs["dzs"][nl - 1]
         if self.classification:
             # fused: logits -> row LSE -> resident-target gather -> dZ
-            idx_t = (
-                self.sampler.stream
-                if hasattr(self.sampler, "stream")
-                else self.sampler.buf
-            )
-            stride = (
-                self.sampler.S if hasattr(self.sampler, "S") else self.B
-            )
+            idx_t, stride = self.sampler.index_ref()
             ext.nll_fused(
                 bufs["acts"][nl - 1], self.Y_all, idx_t, dz, loss_buf,
                 graph_offs, pit, stride,
@@ -967,6 +982,18 @@ def _edge_key(pr):
     return tuple(sorted(map(tuple, map(sorted, pr.graph.edges()))))
 
 
+def _cached_plan(driver, build_fn):
+    """The driver's round plan for the current graph: built by build_fn
+    on first sight of an edge set, cached for the first 256 of them."""
+    key = _edge_key(driver.pr)
+    plan = driver._plans.get(key)
+    if plan is None:
+        plan = build_fn()
+        if len(driver._plans) < 256:
+            driver._plans[key] = plan
+    return plan
+
+
 class DiNNOStackedDriver:
     """DiNNO outer loop with the fused kernels (same math as
     optimizers/dinno.py).
@@ -1035,19 +1062,14 @@ class DiNNOStackedDriver:
                 pass
 
     def _round_plan(self):
-        key = _edge_key(self.pr)
-        plan = self._plans.get(key)
-        if plan is not None:
-            return plan
-        eng = self.eng
-        remote_nodes, rbuf, dests = eng.remote_plan()
-        row_of = eng.row_map(remote_nodes)
-        offs, idx, _ = eng.build_csr(row_of, include_self=False)
-        deg = eng.degrees()
-        plan = (rbuf, dests, offs, idx, deg)
-        if len(self._plans) < 256:
-            self._plans[key] = plan
-        return plan
+        def build():
+            eng = self.eng
+            remote_nodes, rbuf, dests = eng.remote_plan()
+            row_of = eng.row_map(remote_nodes)
+            offs, idx, _ = eng.build_csr(row_of, include_self=False)
+            return rbuf, dests, offs, idx, eng.degrees()
+
+        return _cached_plan(self, build)
 
     def _graph_body(self, rbuf, offs, idx, deg):
         """One DiNNO round with all round-varying scalars read from
@@ -1176,20 +1198,9 @@ class DiNNOStackedDriver:
         )
 
         want_tl = bool(getattr(pr, "track_tloss", False))
-        fused = eng.fused_step_available()
         for pi in range(self.pits):
             wl = want_tl and pi == self.pits - 1
-            if fused:
-                with _timer("train_step"):
-                    off = eng.fused_advance()
-                    lb = eng.run_fused_mnist(off=off, want_loss=wl)
-                grad_t, nparts = eng.grad_parts, eng.fused_nparts
-            else:
-                with _timer("next_batch"):
-                    xb, yb = eng.next_batch()
-                with _timer("fwd_bwd"):
-                    lb = eng.fwd_bwd(xb, yb, want_loss=wl)
-                grad_t, nparts = eng.grad, 1
+            lb, grad_t, nparts = eng.train_step(want_loss=wl)
             if wl and lb is not None:
                 eng.update_tloss(lb)
             with _timer("fused_step"):
@@ -1238,21 +1249,17 @@ class DSGDStackedDriver:
         self._plans = {}
 
     def _round_plan(self):
-        from ..utils import graph_generation
+        def build():
+            from ..utils import graph_generation
 
-        key = _edge_key(self.pr)
-        plan = self._plans.get(key)
-        if plan is not None:
-            return plan
-        eng = self.eng
-        W = graph_generation.get_metropolis(self.pr.graph)
-        remote_nodes, rbuf, dests = eng.remote_plan()
-        row_of = eng.row_map(remote_nodes)
-        offs, idx, w = eng.build_csr(row_of, include_self=True, W=W)
-        plan = (rbuf, dests, offs, idx, w)
-        if len(self._plans) < 256:
-            self._plans[key] = plan
-        return plan
+            eng = self.eng
+            W = graph_generation.get_metropolis(self.pr.graph)
+            remote_nodes, rbuf, dests = eng.remote_plan()
+            row_of = eng.row_map(remote_nodes)
+            offs, idx, w = eng.build_csr(row_of, include_self=True, W=W)
+            return rbuf, dests, offs, idx, w
+
+        return _cached_plan(self, build)
 
     def step_round(self, k):
         opt, pr, eng = self.opt, self.pr, self.eng
@@ -1268,13 +1275,7 @@ class DSGDStackedDriver:
         eng.theta, self.theta_next = self.theta_next, eng.theta
 
         want_tl = bool(getattr(pr, "track_tloss", False))
-        if eng.fused_step_available():
-            off = eng.fused_advance()
-            lb = eng.run_fused_mnist(off=off, want_loss=want_tl)
-            eng.reduce_fused_grad()
-        else:
-            xb, yb = eng.next_batch()
-            lb = eng.fwd_bwd(xb, yb, want_loss=want_tl)
+        lb = eng.train_step_reduced(want_loss=want_tl)
         if want_tl and lb is not None:
             eng.update_tloss(lb)
         ext.axpy(eng.theta, eng.grad, -self.alph, True)
@@ -1310,37 +1311,30 @@ class DSGTStackedDriver:
         self.theta_next = torch.empty_like(eng.theta)
         self._plans = {}
         if self.opt.conf["init_grads"]:
-            if eng.fused_step_available():
-                eng.run_fused_mnist(off=eng.fused_advance())
-                eng.reduce_fused_grad()
-            else:
-                xb, yb = eng.next_batch()
-                eng.fwd_bwd(xb, yb)
+            eng.train_step_reduced()
             self.y.copy_(eng.grad)
             self.g.copy_(eng.grad)
 
     def _round_plan(self):
-        from ..utils import graph_generation
+        def build():
+            from ..utils import graph_generation
 
-        key = _edge_key(self.pr)
-        plan = self._plans.get(key)
-        if plan is not None:
-            return plan
-        eng = self.eng
-        W = graph_generation.get_metropolis(self.pr.graph)
-        remote_nodes, rbuf, _ = eng.remote_plan(width_factor=2)
-        # destination views: [p | y] halves of each remote bundle row
-        n = eng.n
-        dests_p = {j: rbuf[r, :n] for r, j in enumerate(remote_nodes)} \
-            if rbuf is not None else {}
-        dests_y = {j: rbuf[r, n:] for r, j in enumerate(remote_nodes)} \
-            if rbuf is not None else {}
-        row_of = eng.row_map(remote_nodes)
-        offs, idx, w = eng.build_csr(row_of, include_self=True, W=W)
-        plan = (rbuf, dests_p, dests_y, offs, idx, w)
-        if len(self._plans) < 256:
-            self._plans[key] = plan
-        return plan
+            eng = self.eng
+            W = graph_generation.get_metropolis(self.pr.graph)
+            remote_nodes, rbuf, _ = eng.remote_plan(width_factor=2)
+            # destination views: [p | y] halves of each remote bundle row
+            n = eng.n
+            dests_p = {
+                j: rbuf[r, :n] for r, j in enumerate(remote_nodes)
+            } if rbuf is not None else {}
+            dests_y = {
+                j: rbuf[r, n:] for r, j in enumerate(remote_nodes)
+            } if rbuf is not None else {}
+            row_of = eng.row_map(remote_nodes)
+            offs, idx, w = eng.build_csr(row_of, include_self=True, W=W)
+            return rbuf, dests_p, dests_y, offs, idx, w
+
+        return _cached_plan(self, build)
 
     def step_round(self, k):
         opt, pr, eng = self.opt, self.pr, self.eng
@@ -1363,16 +1357,7 @@ class DSGTStackedDriver:
             eng.theta, self.theta_next = self.theta_next, eng.theta
 
         want_tl = bool(getattr(pr, "track_tloss", False))
-        if eng.fused_step_available():
-            with _timer("train_step"):
-                off = eng.fused_advance()
-                lb = eng.run_fused_mnist(off=off, want_loss=want_tl)
-                eng.reduce_fused_grad()
-        else:
-            with _timer("next_batch"):
-                xb, yb = eng.next_batch()
-            with _timer("fwd_bwd"):
-                lb = eng.fwd_bwd(xb, yb, want_loss=want_tl)
+        lb = eng.train_step_reduced(want_loss=want_tl)
         if want_tl and lb is not None:
             eng.update_tloss(lb)
         with _timer("y_update"):

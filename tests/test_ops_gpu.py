@@ -183,6 +183,60 @@ def test_linear_bwd(ext, dtype, L, M, I, O):
 
 @requires_gpu
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize(
+    "M,I,O",
+    [   # one shape on each side of each dW dispatch boundary
+        (255, 16, 16),    # small
+        (256, 16, 16),    # MFMA
+        (256, 16, 64),    # direct
+        (256, 18, 16),    # MFMA, I not a multiple of 16
+        (2048, 8, 8),     # small
+        (2049, 8, 8),     # small-chunked
+        (2049, 2, 256),   # skinny-I exact
+        (2049, 3, 32),    # skinny-I
+        (2049, 32, 2),    # skinny-O
+    ],
+)
+def test_dw_accumulates_matches_kernel(ext, dtype, M, I, O):
+    """dw_accumulates() is the zeroing precondition of linear_bwd_dw:
+    where it is false the kernel overwrites a sentinel-filled slice,
+    where it is true a zeroed slice ends at the same reference; the
+    rest of the row is never touched.
+
+    Inputs are uniform in [-0.25, 0.25]: an M-term fp32 sum of their
+    products (std 1/48 each) then carries at most about
+    6e-8 * (M / sqrt(2)) / 48 = 1.8e-6 of rounding error at M = 2049
+    even summed strictly in sequence, 10x under TOL's fp32 atol, while
+    the sums themselves (std 0.94) are far above it. The reference is
+    the fp64 einsum of the dtype-rounded inputs."""
+    L, pad_lo, pad_hi, sentinel = 2, 64, 7, 1000.0  # |dW| <= M/16 < 1000
+    acc = ext.dw_accumulates(M, I, O)
+    # the rule the stacked engine used before it asked the extension
+    assert acc == ((M >= 256 and I >= 16 and O >= 16) or M > 2048)
+    torch.manual_seed(5)
+    dev = _dev()
+    X = (torch.rand(L * M, I, device=dev) * 0.5 - 0.25).to(dtype)
+    dZ = (torch.rand(L * M, O, device=dev) * 0.5 - 0.25).to(dtype)
+    w_off, b_off = pad_lo, pad_lo + I * O
+    end = b_off + O
+    g = torch.full((L, end + pad_hi), sentinel, dtype=dtype, device=dev)
+    if acc:
+        g[:, w_off:end].zero_()
+    ext.linear_bwd_dw(dZ, X, g, w_off, b_off, M, I, O)
+
+    dz3 = dZ.double().reshape(L, M, O)
+    dW = torch.einsum("lmo,lmi->loi", dz3, X.double().reshape(L, M, I))
+    ref = torch.cat([dW.reshape(L, O * I), dz3.sum(dim=1)], dim=1)
+    got = g[:, w_off:end]
+    print(f"dw {M}x{I}x{O} {dtype} acc={acc} max|err| = "
+          f"{(got.double() - ref).abs().max().item():.3e}")
+    torch.testing.assert_close(got, ref.to(dtype), **TOL[dtype])
+    assert (g[:, :w_off] == sentinel).all()
+    assert (g[:, end:] == sentinel).all()
+
+
+@requires_gpu
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
 @pytest.mark.parametrize("K", [3, 5, 7])
 def test_conv_pool_fwd_bwd(ext, dtype, K):
     # K=5/7 hit the exact KMAX template instantiations; K=3 exercises

@@ -12,14 +12,36 @@ namespace conv {
 // X: [L*B, 28*28]; theta: [L, n] flat stack, W at w_off ([F,1,k,k]
 // row-major = [F, k*k]), b at b_off; Y: [L*B, F*P*P] pooled+ReLU output;
 // idx: [L*B, F*P*P] argmax position (0..3) for pool backward.
-// Grid: one block per image, 256 threads. KMAX bounds the tap loops at
-// compile time (K<=KMAX checked by the caller) so they fully unroll.
+// Grid: one block per image, 256 threads (the launch bound). KMAX bounds
+// the tap loops at compile time (K<=KMAX checked by the caller) so they
+// fully unroll.
 // src_idx != null: the image rows GATHER straight from the resident
 // dataset (X = X_all [L, maxlen, IMG*IMG], row = src_idx[l*idx_stride
 // + idx_off + b]) — the separate gather_batch launch and the xb
 // buffer round-trip disappear from the fused-fc train path.
+//
+// Staging: the weight/bias loads do not depend on the index stream, so
+// their first batch is issued BEFORE the src_idx -> image-row two-hop
+// and lands under it; the image then loads in batches of four
+// independent elements per thread (one L2 round trip for a 28x28 image
+// on 256 threads, not one per 256 elements).
+//
+// Two block-uniform compute paths, chosen from the runtime K:
+//  * K == KMAX (the model's K=5; K=7): one thread per POOLED PIXEL. It
+//    reads the pixel's (K+1)x(K+1) image window from LDS into registers
+//    once; the four pool positions are the four KxK sub-windows of it.
+//    Per filter the K*K weights are read into registers (wave-uniform
+//    LDS reads) and 4*K*K FMAs run back to back: no runtime tap guards,
+//    so no branch or LDS wait between taps.
+//  * K < KMAX (K=3, 4, 6): one thread per (filter, pooled pixel) with
+//    runtime `break` guards in the unrolled tap loops. Every tap is then
+//    its own LDS read -> wait -> FMA -> branch, which is why the
+//    model's shape does not run here.
+// Both sum each conv position as bias first, then taps row-major, one
+// FMA each; ties keep the first pool position (strict >), and a window
+// with no positive position gives Y=0, idx=0.
 template <typename T, int KMAX>
-__global__ void conv_pool_fwd_k(
+__global__ __launch_bounds__(256) void conv_pool_fwd_k(
     const T* __restrict__ X, const T* __restrict__ theta,
     T* __restrict__ Y, unsigned char* __restrict__ idx,
     long n, long w_off, long b_off, int B, int F, int K, int IMG,
@@ -33,31 +55,102 @@ __global__ void conv_pool_fwd_k(
   const long l = lb / B;
   const int conv_out = IMG - (K - 1);
   const int P = conv_out / 2;
+  const int tid = threadIdx.x;
+  const int nthr = blockDim.x;
 
-  // stage image + this node's conv weights/bias
+  // this node's conv weights then bias, as one [F*K*K + F] image; the
+  // first nthr elements (all 78 at the model's shape) load now
+  const T* Wg = theta + l * n + w_off;
+  const T* bg = theta + l * n + b_off;
+  const int nw = F * K * K;
+  const int nwb = nw + F;
+  const auto wload = [&](int t) { return t < nw ? Wg[t] : bg[t - nw]; };
+  const T w_first = tid < nwb ? wload(tid) : T(0);
+
   const long src_row =
       src_idx ? l * maxlen + src_idx[l * idx_stride + idx_off + lb % B]
               : lb;
-  for (int t = threadIdx.x; t < IMG * IMG; t += blockDim.x) {
-    img[t] = X[src_row * IMG * IMG + t];
+  const T* src = X + src_row * IMG * IMG;
+  const int npix = IMG * IMG;
+  // clamped addresses: the four loads of a batch issue unconditionally,
+  // back to back; only the LDS writes are bounds-guarded
+  const auto ldbatch = [&](int t0, T (&v)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int t = t0 + j * nthr + tid;
+      v[j] = src[t < npix ? t : npix - 1];
+    }
+  };
+  const auto stbatch = [&](int t0, const T (&v)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int t = t0 + j * nthr + tid;
+      if (t < npix) img[t] = v[j];
+    }
+  };
+  {
+    T v[4];
+    ldbatch(0, v);
+    if (tid < nwb) wgt[tid] = w_first;
+    stbatch(0, v);
   }
-  const T* Wg = theta + l * n + w_off;
-  const T* bg = theta + l * n + b_off;
-  for (int t = threadIdx.x; t < F * K * K; t += blockDim.x) {
-    wgt[t] = Wg[t];
+  for (int t0 = 4 * nthr; t0 < npix; t0 += 4 * nthr) {
+    T v[4];
+    ldbatch(t0, v);
+    stbatch(t0, v);
   }
-  for (int t = threadIdx.x; t < F; t += blockDim.x) {
-    wgt[F * K * K + t] = bg[t];
-  }
+  for (int t = nthr + tid; t < nwb; t += nthr) wgt[t] = wload(t);
   __syncthreads();
 
-  const int npool = F * P * P;
-  for (int t = threadIdx.x; t < npool; t += blockDim.x) {
-    const int f = t / (P * P);
+  const int PP = P * P;
+  const int npool = F * PP;
+  if (K == KMAX) {
+    constexpr int WN = KMAX + 1;
+    for (int t = tid; t < PP; t += nthr) {
+      const int py = t / P;
+      const int px = t % P;
+      const T* wbase = img + (2 * py) * IMG + 2 * px;
+      T win[WN * WN];
+#pragma unroll
+      for (int r = 0; r < WN; ++r) {
+#pragma unroll
+        for (int c = 0; c < WN; ++c) win[r * WN + c] = wbase[r * IMG + c];
+      }
+      for (int f = 0; f < F; ++f) {
+        T w[KMAX * KMAX];
+#pragma unroll
+        for (int i = 0; i < KMAX * KMAX; ++i) {
+          w[i] = wgt[f * KMAX * KMAX + i];
+        }
+        const T bias = wgt[nw + f];
+        T best = T(0);       // ReLU floor: max(0, .) pooled
+        int best_i = 0;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          T acc = bias;
+#pragma unroll
+          for (int ky = 0; ky < KMAX; ++ky) {
+#pragma unroll
+            for (int kx = 0; kx < KMAX; ++kx) {
+              acc += win[((d >> 1) + ky) * WN + (d & 1) + kx] *
+                     w[ky * KMAX + kx];
+            }
+          }
+          if (acc > best) { best = acc; best_i = d; }
+        }
+        Y[lb * npool + f * PP + t] = best;
+        idx[lb * npool + f * PP + t] = (unsigned char)best_i;
+      }
+    }
+    return;
+  }
+
+  for (int t = tid; t < npool; t += nthr) {
+    const int f = t / PP;
     const int py = (t / P) % P;
     const int px = t % P;
     const T* wf = wgt + f * K * K;
-    const T bias = wgt[F * K * K + f];
+    const T bias = wgt[nw + f];
 
     T best = T(0);       // ReLU floor: max(0, .) pooled
     int best_i = 0;

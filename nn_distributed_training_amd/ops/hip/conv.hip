@@ -7,6 +7,8 @@
 
 #include "common.h"
 
+#include <type_traits>
+
 namespace conv {
 
 // X: [L*B, 28*28]; theta: [L, n] flat stack, W at w_off ([F,1,k,k]
@@ -177,6 +179,83 @@ __global__ __launch_bounds__(256) void conv_pool_fwd_k(
   }
 }
 
+// One level of the multi-value wave reduction below: N partials per
+// lane become N/2. Lanes whose bit D is clear keep the even slot of
+// each pair and send the odd one to lane^D; lanes with the bit set do
+// the opposite; each adds what it receives. Slots at or past NREAL are
+// compile-time zeros: a pair of two such slots needs no exchange. All
+// subscripts are compile-time (the lane bit only drives selects), so
+// the partials stay in registers.
+template <typename T, int S, int N, int NREAL, int D>
+DEV_INLINE void wave_halve_slots(T (&v)[S], bool hi) {
+  constexpr int NX = (NREAL + 1) / 2;  // exchanges at this level
+  T recv[NX];
+#pragma unroll
+  for (int j = 0; j < NX; ++j) {
+    const T a = v[2 * j];
+    const T b = (2 * j + 1 < NREAL) ? v[2 * j + 1] : T(0);
+    recv[j] = __shfl_xor(hi ? a : b, D, WAVE);
+  }
+  // every exchange of the level is issued before the first add waits
+  // on one (left alone the scheduler pairs them up, and the level
+  // becomes NX/2 dependent LDS-crossbar round trips instead of one)
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int j = 0; j < NX; ++j) {
+    const T a = v[2 * j];
+    const T b = (2 * j + 1 < NREAL) ? v[2 * j + 1] : T(0);
+    v[j] = (hi ? b : a) + recv[j];
+  }
+}
+
+template <typename T, int S, int N, int NREAL, int D>
+DEV_INLINE void wave_reduce_slots_from(T (&v)[S], int lane) {
+  if constexpr (D >= 1) {
+    if constexpr (N > 1) {
+      wave_halve_slots<T, S, N, NREAL, D>(v, (lane & D) != 0);
+      wave_reduce_slots_from<T, S, N / 2, (NREAL + 1) / 2, D / 2>(v, lane);
+    } else {
+      v[0] += __shfl_xor(v[0], D, WAVE);
+      wave_reduce_slots_from<T, S, 1, 1, D / 2>(v, lane);
+    }
+  }
+}
+
+// Wave-wide sums of NREAL per-lane partials v[0..NREAL) at once, as a
+// halving butterfly: S (a power of two, NREAL <= S <= WAVE) slots are
+// halved at xor distances 32, 16, ... until one is left, and any
+// distances that remain are plain xor adds. That is S-1 exchanges (fewer
+// with padding) in a dependent chain log2(WAVE) deep, where one
+// wave_reduce_sum per slot is 6*NREAL exchanges in a chain as long.
+// Returns the wave total of slot wave_slot_of<S>(lane) in every lane.
+template <typename T, int S, int NREAL>
+DEV_INLINE T wave_reduce_slots(T (&v)[S], int lane) {
+  static_assert(S >= 2 && S <= WAVE && (S & (S - 1)) == 0, "bad S");
+  static_assert(NREAL >= 1 && NREAL <= S, "bad NREAL");
+  wave_reduce_slots_from<T, S, S, NREAL, WAVE / 2>(v, lane);
+  return v[0];
+}
+
+// The slot whose total wave_reduce_slots leaves in `lane`: the first
+// level hands slot parity to lane bit 5, the next one to bit 4, ..., so
+// the slot number is the lane's top log2(S) bits reversed (lanes that
+// differ only in the bits below hold the same total).
+template <int S>
+DEV_INLINE int wave_slot_of(int lane) {
+  int s = 0;
+#pragma unroll
+  for (int bit = 1, d = WAVE / 2; bit < S; bit <<= 1, d >>= 1) {
+    if (lane & d) s |= bit;
+  }
+  return s;
+}
+
+constexpr int pow2_at_least(int x) {
+  int p = 1;
+  while (p < x) p <<= 1;
+  return p;
+}
+
 // Backward to weights/bias: route each pooled grad to its argmax conv
 // position, multiply by the image window. dY is the grad AFTER the relu
 // mask (pooled output > 0), applied by the caller via act_grad.
@@ -184,9 +263,19 @@ __global__ __launch_bounds__(256) void conv_pool_fwd_k(
 // Grid: (l, f, batch-chunk) so the chip fills (the v1 one-block-per-
 // (l,f) version was 24 blocks on 256 CUs and 41% of round time);
 // each thread accumulates a private dW[K*K]+db over its strided share
-// of the chunk, waves shuffle-reduce, wave leaders combine in LDS and
-// lane 0 atomically adds into the grad stack (the caller zeroes the
-// conv slice first).
+// of the chunk, each wave reduces its K*K+1 partials with one halving
+// butterfly (wave_reduce_slots), the lanes left holding a total park it
+// in LDS, and after ONE barrier the first KMAX*KMAX+1 threads combine
+// the waves and atomically add into the grad stack (the caller zeroes
+// the conv slice first).
+//
+// Two block-uniform compute paths, chosen from the runtime K:
+//  * K == KMAX: no zero-grad skip and no runtime breaks, so the K*K
+//    image loads of an item issue back to back. An item is two
+//    dependent round trips: its (g, argmax) header together with its
+//    source-row index, then its taps.
+//  * K < KMAX: one item at a time with a zero-grad skip and runtime
+//    `break` guards in the unrolled tap loops.
 //
 // The body takes its block index `bid`, thread index `tid`, block size
 // `nthr` (a multiple of 64, at most 256) and its LDS scratch `red`
@@ -200,6 +289,8 @@ DEV_INLINE void conv_pool_bwd_body(
     int nchunk,
     const long* __restrict__ src_idx, long idx_stride, long idx_off,
     long maxlen, int bid, int tid, int nthr, T* __restrict__ red) {
+  constexpr int NTAP = KMAX * KMAX;
+  constexpr int NSLOT = pow2_at_least(NTAP + 1);
   const int chunk = bid % nchunk;
   const int f = (bid / nchunk) % F;
   const int l = bid / (nchunk * F);
@@ -210,59 +301,51 @@ DEV_INLINE void conv_pool_bwd_body(
   const int b0 = chunk * cb;
   const int b1 = min(B, b0 + cb);
 
-  T dw[KMAX * KMAX];
-  T db = T(0);
-  #pragma unroll
-  for (int i = 0; i < KMAX * KMAX; ++i) dw[i] = T(0);
+  // acc[0..NTAP) = dW taps (KMAX-strided), acc[NTAP] = db; the rest is
+  // the butterfly's padding and is never read
+  T acc[NSLOT];
+#pragma unroll
+  for (int i = 0; i <= NTAP; ++i) acc[i] = T(0);
 
   const int work = (b1 - b0) * P * P;
   if (K == KMAX) {
-    // exact-K fast path: no per-element zero-skip branch and no
-    // runtime breaks inside the unrolled GLOBAL-load chain — both
-    // forced per-element branch + vmcnt waits around the 25 img loads
-    // (trap 4c); unconditional taps pipeline (g = 0 contributes 0).
-    // The (g, pool-argmax) pair for iteration t+1 prefetches while
-    // iteration t's taps run — idx[o] -> img-address is a 2-hop
-    // dependency that otherwise heads every iteration (loads use a
-    // CLAMPED index so the prefetch needs no bounds branch).
-    auto hdr = [&](long t, T& g, int& d, long& b) {
-      const long tc = t < work ? t : (work > 0 ? work - 1 : 0);
-      b = b0 + tc / (P * P);
-      const long o = ((long)l * B + b) * npool + f * P * P
-                     + ((tc / P) % P) * P + tc % P;
-      g = dY[o];
-      d = idx[o];
-    };
-    long t = tid;
-    T g = T(0);
-    int d = 0;
-    long b = 0;
-    if (work > 0) hdr(t, g, d, b);
-    for (; t < work; t += nthr) {
-      T gn;
-      int dn;
-      long bn;
-      hdr(t + nthr, gn, dn, bn);
-      const int py = (int)((t / P) % P);
-      const int px = (int)(t % P);
-      const int cy = 2 * py + (d >> 1);
-      const int cx = 2 * px + (d & 1);
-      const long src_row =
-          src_idx ? l * maxlen + src_idx[l * idx_stride + idx_off + b]
-                  : (long)l * B + b;
-      const T* img = X + src_row * IMG * IMG;
-      db += g;
+    // no per-element zero-skip branch and no runtime breaks inside the
+    // unrolled GLOBAL-load chain — both forced per-element branch +
+    // vmcnt waits around the K*K img loads (trap 4c); unconditional
+    // taps pipeline (g = 0 contributes 0).
+    // An item's header (g, argmax) and its source-row index load
+    // together; the K*K taps follow as the second round trip. The
+    // src_idx test is hoisted around the whole loop: as a branch inside
+    // the iteration it puts a vmcnt(0) wait between the header loads.
+    const auto run = [&](auto indexed) {
+      for (int t = tid; t < work; t += nthr) {
+        const int b = b0 + t / (P * P);
+        const int pyx = t % (P * P);
+        const long lb = (long)l * B + b;
+        const long o = lb * npool + f * P * P + pyx;
+        const T g = dY[o];
+        const int d = idx[o];
+        long row = lb;
+        if constexpr (decltype(indexed)::value) {
+          row = l * maxlen + src_idx[l * idx_stride + idx_off + b];
+        }
+        const int cy = 2 * (pyx / P) + (d >> 1);
+        const int cx = 2 * (pyx % P) + (d & 1);
+        const T* img = X + row * IMG * IMG + cy * IMG + cx;
+        acc[NTAP] += g;
 #pragma unroll
-      for (int ky = 0; ky < KMAX; ++ky) {
-        const T* row = img + (cy + ky) * IMG + cx;
+        for (int ky = 0; ky < KMAX; ++ky) {
 #pragma unroll
-        for (int kx = 0; kx < KMAX; ++kx) {
-          dw[ky * KMAX + kx] += g * row[kx];
+          for (int kx = 0; kx < KMAX; ++kx) {
+            acc[ky * KMAX + kx] += g * img[ky * IMG + kx];
+          }
         }
       }
-      g = gn;
-      d = dn;
-      b = bn;
+    };
+    if (src_idx) {
+      run(std::true_type{});
+    } else {
+      run(std::false_type{});
     }
   } else {
     for (int t = tid; t < work; t += nthr) {
@@ -280,9 +363,9 @@ DEV_INLINE void conv_pool_bwd_body(
           src_idx ? l * maxlen + src_idx[l * idx_stride + idx_off + b]
                   : lb;
       const T* img = X + src_row * IMG * IMG;
-      db += g;
+      acc[NTAP] += g;
       // compile-time bounds + KMAX-strided indices: a runtime
-      // `ky*K+kx` subscript makes dw[] dynamically indexed and the
+      // `ky*K+kx` subscript makes acc[] dynamically indexed and the
       // compiler spills the whole accumulator to scratch (rule 20)
 #pragma unroll
       for (int ky = 0; ky < KMAX; ++ky) {
@@ -291,40 +374,40 @@ DEV_INLINE void conv_pool_bwd_body(
 #pragma unroll
         for (int kx = 0; kx < KMAX; ++kx) {
           if (kx >= K) break;
-          dw[ky * KMAX + kx] += g * row[kx];
+          acc[ky * KMAX + kx] += g * row[kx];
         }
       }
     }
   }
 
-  // reduce the K*K+1 partials: shuffle-reduce every tap within its
-  // wave (no barriers), park the per-wave sums in LDS, then ONE
-  // barrier and the first KMAX*KMAX+1 threads finish their tap in
-  // parallel. The previous per-tap LDS tree spent 2 barriers per tap
-  // (52 for K=5) and dominated the kernel.
+  // reduce the K*K+1 partials: one butterfly per wave (no barriers; a
+  // lane without items, a wave without items and a tap skipped because
+  // K < KMAX all carry exact zeros), the lane that ends up with a
+  // slot's wave total parks it in LDS, then ONE barrier and the first
+  // KMAX*KMAX+1 threads finish their tap in parallel. Skipped taps are
+  // neither parked nor added.
   // red: [tap][wave]
   const int lane = tid & (WAVE - 1);
   const int wid = tid / WAVE;
   T* wslice = gstack + (long)l * n + w_off + (long)f * K * K;
-#pragma unroll
-  for (int i = 0; i < KMAX * KMAX + 1; ++i) {
-    const int ky = i / KMAX, kx = i % KMAX;
-    const bool is_db = (i == KMAX * KMAX);
-    if (!is_db && (ky >= K || kx >= K)) continue;  // uniform
-    const T v = wave_reduce_sum(is_db ? db : dw[i]);
-    if (lane == 0) red[i * 4 + wid] = v;
+  const auto live = [&](int i) {
+    return i == NTAP || (i < NTAP && i / KMAX < K && i % KMAX < K);
+  };
+  {
+    const T tot = wave_reduce_slots<T, NSLOT, NTAP + 1>(acc, lane);
+    const int i = wave_slot_of<NSLOT>(lane);
+    const bool owner = (lane & (WAVE / NSLOT - 1)) == 0;
+    if (owner && live(i)) red[i * 4 + wid] = tot;
   }
   __syncthreads();
-  for (int i = tid; i < KMAX * KMAX + 1; i += nthr) {
-    const int ky = i / KMAX, kx = i % KMAX;
-    const bool is_db = (i == KMAX * KMAX);
-    if (!is_db && (ky >= K || kx >= K)) continue;
+  for (int i = tid; i < NTAP + 1; i += nthr) {
+    if (!live(i)) continue;
     const T tot =
         red[i * 4] + red[i * 4 + 1] + red[i * 4 + 2] + red[i * 4 + 3];
-    if (is_db) {
+    if (i == NTAP) {
       atomicAdd(&gstack[(long)l * n + b_off + f], tot);
     } else {
-      atomicAdd(&wslice[ky * K + kx], tot);
+      atomicAdd(&wslice[(i / KMAX) * K + i % KMAX], tot);
     }
   }
 }

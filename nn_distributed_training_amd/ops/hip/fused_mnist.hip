@@ -708,11 +708,13 @@ __global__ __launch_bounds__(512) void fc_block_k(
 // dW blocks of the MNIST shape share the chip with the 768 conv blocks.
 // Blocks [0, n_dw) decode to the dW kernel's (bx, by, bz) grid, the
 // rest to the conv kernel's block index; the role branch is
-// block-uniform and the LDS arena is the larger of the two needs.
-// No occupancy bound beyond the block size: the conv role needs ~100
+// block-uniform and the LDS arena is the larger of the two needs
+// (two [64][17] dW tiles, or the conv role's [K*K+1][4] wave sums).
+// No occupancy bound beyond the block size: the conv role needs ~110
 // VGPRs in fp64 (4 blocks/CU) and forcing 8 waves/SIMD spills its dW
-// accumulators to scratch. The short dW blocks come first in the grid
-// and retire quickly, so the conv blocks fill in behind them.
+// accumulators to scratch. The short dW blocks (one load round trip
+// and one barrier at M = 64) come first in the grid and retire
+// quickly, so the conv blocks fill in behind them.
 template <typename T, int KMAX>
 __global__ __launch_bounds__(256) void dw_conv_bwd_k(
     // dW role
@@ -725,7 +727,7 @@ __global__ __launch_bounds__(256) void dw_conv_bwd_k(
     int IMG, int nchunk, const long* __restrict__ src_idx,
     long idx_stride, long idx_off, long maxlen,
     T* __restrict__ gstack, long n) {
-  constexpr int DW_LDS = 2 * gemm::TILE * (gemm::TILE + 1);
+  constexpr int DW_LDS = 2 * gemm::DW_ROWS * (gemm::TILE + 1);
   constexpr int CV_LDS = (KMAX * KMAX + 1) * 4;
   __shared__ T smem[DW_LDS > CV_LDS ? DW_LDS : CV_LDS];
   const int bid = blockIdx.x;
@@ -737,7 +739,7 @@ __global__ __launch_bounds__(256) void dw_conv_bwd_k(
     gemm::linear_bwd_dw_body<T>(
         dZ, X, gstack, n, w_off, b_off, M, I, O, bx, by, bz,
         tid / gemm::TILE, tid % gemm::TILE, smem,
-        smem + gemm::TILE * (gemm::TILE + 1));
+        smem + gemm::DW_ROWS * (gemm::TILE + 1));
   } else {
     conv::conv_pool_bwd_body<T, KMAX>(
         dY, pidx, X_all, gstack, n, cw_off, cb_off, M, F, K, IMG,

@@ -204,13 +204,24 @@ __global__ void linear_bwd_dx_k(
 
 // dW[O,I] = dZ_l[M,O]^T @ X_l[M,I], written into the [L, n] grad stack
 // at the layer's offset; db[O] (column sums of dZ) is fused: the i0==0
-// block column accumulates bias partials from its staged dZ tiles while
-// it loops over M (the separate bias kernel was an underfilled launch).
+// block column sums bias partials from the dZ rows it stages.
+//
+// K (= M, the batch) is staged DW_ROWS = 64 rows at a time: each thread
+// issues its four dZ and four X loads (rows k0+to, +16, +32, +48) back
+// to back, then one barrier, then 64 FMAs with k ascending. The model's
+// M = 64 is therefore one global round trip and one barrier (the
+// 16-row version walked four of each, one after the other). A pass
+// whose 64 rows and 16x16 output tile are all in range loads without
+// guards; edge passes zero-fill. M > 64 loops over passes, with a
+// second barrier only between passes.
 // The body takes its block (bx, by, bz) and thread (to, ti) coordinates
-// and its two [TILE][TILE+1] LDS tiles as arguments, so the merged
+// and its two [DW_ROWS][TILE+1] LDS tiles as arguments, so the merged
 // backward launch (fused_mnist.hip dw_conv_bwd_k) can run it as one
-// role of a flat grid; the summation order is the same wherever it is
-// called from.
+// role of a flat grid; the summation order (m ascending per output
+// element; bias rows m = to, to+16, ... ascending, then to ascending)
+// is the same wherever it is called from.
+constexpr int DW_ROWS = 4 * TILE;
+
 template <typename T>
 DEV_INLINE void linear_bwd_dw_body(
     const T* __restrict__ dZ, const T* __restrict__ X,
@@ -225,24 +236,40 @@ DEV_INLINE void linear_bwd_dw_body(
   const int o0 = by * TILE;
   const int i0 = bx * TILE;
   const bool bias_block = (i0 == 0);
+  const bool full_tile = (o0 + TILE <= O) && (i0 + TILE <= I);
+  const int o_ld = o0 + ti, i_ld = i0 + ti;
 
   T acc = T(0);
   T bacc = T(0);  // thread (to, ti): partial db[o0+ti] over rows m≡to
-  for (int k0 = 0; k0 < M; k0 += TILE) {
-    {
-      const int m = k0 + to;
-      const int o = o0 + ti;
-      gs[to * TP + ti] = (m < M && o < O) ? dZl[(long)m * O + o] : T(0);
-      const int i = i0 + ti;
-      xs[to * TP + ti] = (m < M && i < I) ? Xl[(long)m * I + i] : T(0);
+  for (int k0 = 0; k0 < M; k0 += DW_ROWS) {
+    if (k0 > 0) __syncthreads();  // the previous pass is done reading
+    T g[4], x[4];
+    if (full_tile && k0 + DW_ROWS <= M) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long m = k0 + to + r * TILE;
+        g[r] = dZl[m * O + o_ld];
+        x[r] = Xl[m * I + i_ld];
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long m = k0 + to + r * TILE;
+        g[r] = (m < M && o_ld < O) ? dZl[m * O + o_ld] : T(0);
+        x[r] = (m < M && i_ld < I) ? Xl[m * I + i_ld] : T(0);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      gs[(to + r * TILE) * TP + ti] = g[r];
+      xs[(to + r * TILE) * TP + ti] = x[r];
+      if (bias_block) bacc += g[r];
     }
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < TILE; ++k) {
+    for (int k = 0; k < DW_ROWS; ++k) {
       acc += gs[k * TP + to] * xs[k * TP + ti];
     }
-    if (bias_block) bacc += gs[to * TP + ti];
-    __syncthreads();
   }
   const int o = o0 + to, i = i0 + ti;
   if (o < O && i < I) {
@@ -250,6 +277,7 @@ DEV_INLINE void linear_bwd_dw_body(
   }
   if (bias_block) {
     // column-sum bacc over to (16 rows) through LDS, thread row 0 writes
+    __syncthreads();  // gs is still being read by the last pass
     gs[to * TP + ti] = bacc;
     __syncthreads();
     if (to == 0 && o0 + ti < O) {
@@ -266,8 +294,8 @@ __global__ void linear_bwd_dw_k(
     const T* __restrict__ dZ, const T* __restrict__ X,
     T* __restrict__ gstack, long n, long w_off, long b_off,
     int M, int I, int O) {
-  __shared__ T gs[TILE * (TILE + 1)];
-  __shared__ T xs[TILE * (TILE + 1)];
+  __shared__ T gs[DW_ROWS * (TILE + 1)];
+  __shared__ T xs[DW_ROWS * (TILE + 1)];
   linear_bwd_dw_body<T>(dZ, X, gstack, n, w_off, b_off, M, I, O,
                         blockIdx.x, blockIdx.y, blockIdx.z,
                         threadIdx.y, threadIdx.x, gs, xs);

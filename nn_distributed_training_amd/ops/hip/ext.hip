@@ -794,6 +794,57 @@ void regression_bwd(torch::Tensor yhat, torch::Tensor tgt,
   HIP_CHECK_LAST();
 }
 
+// PPO clipped surrogate + critic MSE backward (losses.hip
+// ppo_loss_bwd_k): mean/acts [L*M, A], the rest [L*M]; loss [L, 2] is
+// accumulated into when given (the caller zeroes it).
+void ppo_loss_bwd(torch::Tensor mean, torch::Tensor acts,
+                  torch::Tensor old_logp, torch::Tensor adv,
+                  torch::Tensor v, torch::Tensor rtgs,
+                  torch::Tensor dmean, torch::Tensor dv,
+                  c10::optional<torch::Tensor> loss, long M, double cov,
+                  double clip, double critic_coef, double loss_scale) {
+  CHECK_DEV(mean); CHECK_DEV(acts); CHECK_DEV(old_logp); CHECK_DEV(adv);
+  CHECK_DEV(v); CHECK_DEV(rtgs); CHECK_DEV(dmean); CHECK_DEV(dv);
+  TORCH_CHECK(mean.dim() == 2, "mean must be [L*M, A]");
+  const long rows = mean.size(0), A = mean.size(1);
+  TORCH_CHECK(A >= 1 && A <= losses::PPO_MAX_A,
+              "ppo_loss_bwd supports action dim <= ", losses::PPO_MAX_A);
+  TORCH_CHECK(M > 0 && rows % M == 0, "rows must be L*M");
+  TORCH_CHECK(cov > 0, "cov must be positive");
+  TORCH_CHECK(acts.numel() == rows * A && dmean.numel() == rows * A,
+              "acts/dmean must match mean");
+  for (const torch::Tensor* t : {&old_logp, &adv, &v, &rtgs, &dv}) {
+    TORCH_CHECK(t->numel() == rows, "per-sample vectors must be [L*M]");
+  }
+  for (const torch::Tensor* t :
+       {&acts, &old_logp, &adv, &v, &rtgs, &dmean, &dv}) {
+    TORCH_CHECK(t->scalar_type() == mean.scalar_type(),
+                "ppo_loss_bwd tensors must share one dtype");
+  }
+  if (loss.has_value()) {
+    CHECK_DEV(*loss);
+    TORCH_CHECK(loss->numel() == 2 * (rows / M) &&
+                    loss->scalar_type() == mean.scalar_type(),
+                "loss must be [L, 2] of the same dtype");
+  }
+  if (rows == 0) return;
+  const double logc =
+      0.5 * (double)A * std::log(2.0 * 3.14159265358979323846 * cov);
+  DISPATCH_FT(mean, {
+    hipLaunchKernelGGL(losses::ppo_loss_bwd_k<scalar_t>,
+        dim3(grid_1d(rows)), dim3(256), 0, cur_stream(),
+        mean.data_ptr<scalar_t>(), acts.data_ptr<scalar_t>(),
+        old_logp.data_ptr<scalar_t>(), adv.data_ptr<scalar_t>(),
+        v.data_ptr<scalar_t>(), rtgs.data_ptr<scalar_t>(),
+        dmean.data_ptr<scalar_t>(), dv.data_ptr<scalar_t>(),
+        opt_ptr<scalar_t>(loss), rows, (int)A, (int)M,
+        (scalar_t)(1.0 / cov), (scalar_t)logc, (scalar_t)(1.0 - clip),
+        (scalar_t)(1.0 + clip), (scalar_t)critic_coef,
+        (scalar_t)loss_scale);
+  });
+  HIP_CHECK_LAST();
+}
+
 // fc1 dW/db + gather-sourced conv dW/db in ONE launch (fused_mnist.hip
 // dw_conv_bwd_k) where the dW shape takes the small store-path kernel;
 // any other shape keeps the two launches. Same preconditions as
@@ -1157,6 +1208,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("mnist_train_step", &mnist_train_step);
   mod.def("bce_bwd", &bce_bwd);
   mod.def("regression_bwd", &regression_bwd);
+  mod.def("ppo_loss_bwd", &ppo_loss_bwd);
   mod.def("feistel_perm", &feistel_perm);
   mod.def("consensus_cdist", &consensus_cdist);
   mod.def("fc_block", &fc_block);

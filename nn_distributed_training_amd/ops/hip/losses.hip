@@ -137,4 +137,93 @@ __global__ void nll_fused_k(
   }
 }
 
+// PPO clipped-surrogate + critic-MSE backward for a fixed-covariance
+// Gaussian policy (covariance = cov * I), all nodes in one launch.
+// Node l owns rows [l*B, (l+1)*B); mean reduction per node. Per row:
+//   logp  = -0.5 * |a - mu|^2 / cov - logc,  logc = 0.5*A*log(2*pi*cov)
+//   r     = exp(logp - old_logp)            (no eps, no exponent clamp:
+//                                            the torch path has none)
+//   actor = -min(r*adv, clamp(r, lo, hi)*adv),  critic = (v - rtg)^2
+//   dmu_j = -loss_scale * g * r * (a_j - mu_j) / cov / B
+//   dv    = loss_scale * critic_coef * 2 * (v - rtg) / B
+// g is torch's subgradient of the min/clamp pair (minimum splits ties,
+// clamp passes the gradient at its bounds): adv inside [lo, hi] and on
+// the side where the unclipped term is the smaller one, else 0.
+// lo/hi arrive already rounded to T, as torch rounds clamp's bounds.
+// loss (may be null, [L, 2], zeroed by the caller) accumulates the
+// per-node means (actor, critic), unscaled. A wave whose 64 rows all
+// belong to one node shuffle-reduces and issues one atomic per term;
+// a wave that straddles a node boundary or the end adds per lane.
+// One thread per row; the row lives in registers (A <= PPO_MAX_A, the
+// guarded full unroll keeps d[] out of scratch).
+constexpr int PPO_MAX_A = 16;
+
+template <typename T>
+__global__ void ppo_loss_bwd_k(
+    const T* __restrict__ mean, const T* __restrict__ acts,
+    const T* __restrict__ old_logp, const T* __restrict__ adv,
+    const T* __restrict__ v, const T* __restrict__ rtgs,
+    T* __restrict__ dmean, T* __restrict__ dv,
+    T* __restrict__ loss,  // may be null, [L, 2]
+    long M, int A, int B, T inv_cov, T logc, T lo, T hi,
+    T critic_coef, T loss_scale) {
+  const T invB = T(1) / T(B);
+  const int lane = threadIdx.x & 63;
+  // wave-uniform trip count: every lane of a wave stays in the loop so
+  // the shuffles below always see 64 active lanes
+  for (long base = blockIdx.x * 256L + (threadIdx.x - lane); base < M;
+       base += (long)gridDim.x * 256L) {
+    const long m = base + lane;
+    const bool valid = m < M;
+    T la = T(0), lc = T(0);
+    if (valid) {
+      const T* mu = mean + m * A;
+      const T* a = acts + m * A;
+      T d[PPO_MAX_A];
+      T sq = T(0);
+#pragma unroll
+      for (int j = 0; j < PPO_MAX_A; ++j) {
+        d[j] = T(0);
+        if (j < A) {
+          d[j] = a[j] - mu[j];
+          sq += d[j] * d[j];
+        }
+      }
+      const T logp = T(-0.5) * sq * inv_cov - logc;
+      const T r = ::exp(logp - old_logp[m]);
+      const T ad = adv[m];
+      const T rc = r < lo ? lo : (r > hi ? hi : r);
+      const T s1 = r * ad, s2 = rc * ad;
+      la = -(s1 < s2 ? s1 : s2) * invB;
+      const bool pass = (r >= lo && r <= hi) ||
+                        (ad > T(0) && r < lo) || (ad < T(0) && r > hi);
+      const T g = pass ? ad : T(0);
+      const T cm = -loss_scale * g * r * inv_cov * invB;
+      T* dm = dmean + m * A;
+#pragma unroll
+      for (int j = 0; j < PPO_MAX_A; ++j) {
+        if (j < A) dm[j] = cm * d[j];
+      }
+      const T e = v[m] - rtgs[m];
+      lc = e * e * invB;
+      dv[m] = loss_scale * critic_coef * T(2) * e * invB;
+    }
+    if (loss != nullptr) {
+      const bool one_node =
+          base + 63 < M && base / B == (base + 63) / B;
+      if (one_node) {
+        la = wave_reduce_sum(la);
+        lc = wave_reduce_sum(lc);
+        if (lane == 0) {
+          atomicAdd(&loss[2 * (base / B)], la);
+          atomicAdd(&loss[2 * (base / B) + 1], lc);
+        }
+      } else if (valid) {
+        atomicAdd(&loss[2 * (m / B)], la);
+        atomicAdd(&loss[2 * (m / B) + 1], lc);
+      }
+    }
+  }
+}
+
 }  // namespace losses

@@ -63,6 +63,10 @@ class DistPPOProblem:
 
         # rollout buffers (per node), populated by rollout()
         self.buf = None
+        # optional hook: an engine with load_obs()/values() (the
+        # optimizers' grad_engine="stacked" attaches its
+        # StackedPPOEngine); rollout() then takes V(obs) from it
+        self.value_engine = None
         self.total_timesteps = 0
         self.ep_rew_history = []  # mean episodic reward per batch
 
@@ -169,14 +173,29 @@ class DistPPOProblem:
                 rtgs, dtype=torch.get_default_dtype(),
                 device=self.device,
             )
-            with torch.no_grad():
-                v = self.critics[i](obs_i).squeeze(-1)
-            adv = rtgs_i - v
-            adv = (adv - adv.mean()) / (adv.std() + 1e-10)
             self.buf[i] = dict(
                 obs=obs_i, acts=acts_i, logp=logp_i, rtgs=rtgs_i,
-                adv=adv,
             )
+            if self.value_engine is None:
+                with torch.no_grad():
+                    v = self.critics[i](obs_i).squeeze(-1)
+                adv = rtgs_i - v
+                adv = (adv - adv.mean()) / (adv.std() + 1e-10)
+                self.buf[i]["adv"] = adv
+        if self.value_engine is not None:
+            # V(obs) of all nodes from the stacked critic forward, then
+            # the same per-node normalization batched over [N, M]
+            eng = self.value_engine
+            eng.load_obs([self.buf[i]["obs"] for i in range(self.N)])
+            v = eng.values(eng.stack_from_modules())
+            adv = torch.stack(
+                [self.buf[i]["rtgs"] for i in range(self.N)]
+            ) - v
+            adv = (adv - adv.mean(dim=1, keepdim=True)) / (
+                adv.std(dim=1, keepdim=True) + 1e-10
+            )
+            for i in range(self.N):
+                self.buf[i]["adv"] = adv[i]
 
     # ------------------------------------------------------------------
     def local_batch_loss(self, i):

@@ -47,8 +47,88 @@ class _PPOBase:
         self.timesteps = []
         self.agreements_actor = []
         self.agreements_critic = []
+        self.grad_engine = conf.get("grad_engine", "torch")
+        self.engine = self._resolve_grad_engine()
 
     # ------------------------------------------------------------------
+    def _resolve_grad_engine(self):
+        """The StackedPPOEngine for ``grad_engine: "stacked"``, None for
+        ``"torch"``. A stacked request that cannot be served is an
+        error, never a quiet per-node run."""
+        if self.grad_engine == "torch":
+            return None
+        if self.grad_engine != "stacked":
+            raise ValueError(
+                f"grad_engine must be 'torch' or 'stacked', got "
+                f"{self.grad_engine!r}"
+            )
+        if self.device.type != "cuda":
+            raise ValueError(
+                "grad_engine='stacked' needs a GPU problem; this one is "
+                f"on {self.device}"
+            )
+        from ..ops import get_ext
+
+        try:
+            get_ext()
+        except Exception as e:  # noqa: BLE001
+            raise ValueError(
+                "grad_engine='stacked' needs the HIP extension, which "
+                f"failed to load: {e}"
+            ) from e
+        from .stacked_ppo import StackedPPOEngine
+
+        engine = StackedPPOEngine(self.pr)
+        # rollout() takes V(obs) for the advantages from the engine
+        self.pr.value_engine = engine
+        return engine
+
+    def _begin_round(self):
+        """Hand the round's rollout to the stacked engine."""
+        if self.engine is not None:
+            self.engine.load_rollout(self.pr.buf)
+
+    def _theta_stack(self):
+        """[N, n] stack of the modules' current node vectors (a copy)."""
+        pr = self.pr
+        return torch.stack(
+            [pr.node_vector(i).detach() for i in range(pr.N)]
+        ).contiguous()
+
+    def _grad_stack(self, theta):
+        """[N, n] PPO gradients at the current parameters ``theta``.
+
+        "torch": per-node autograd through the actor/critic modules,
+        which the caller keeps equal to ``theta`` (a fresh tensor).
+        "stacked": ``StackedPPOEngine.grads(theta)`` - no module, no
+        autograd; the result is the engine's buffer, overwritten by the
+        next call."""
+        if self.engine is not None:
+            return self.engine.grads(theta)
+        pr = self.pr
+        grads = []
+        for i in range(pr.N):
+            for p in pr.node_parameters(i):
+                p.grad = None
+            pred_loss = pr.local_batch_loss(i)
+            pred_loss.backward()
+            grads.append(
+                torch.cat(
+                    [
+                        (p.grad if p.grad is not None
+                         else torch.zeros_like(p)).reshape(-1)
+                        for p in pr.node_parameters(i)
+                    ]
+                )
+            )
+        return torch.stack(grads).to(theta.dtype).contiguous()
+
+    def _write_back(self, theta):
+        """Load the stack rows into the actor/critic modules."""
+        with torch.no_grad():
+            for i in range(self.pr.N):
+                self.pr.set_node_vector(i, theta[i].clone())
+
     def _snapshot_vectors(self):
         return {
             i: self.pr.node_vector(i).detach().clone()
@@ -181,16 +261,20 @@ class DiNNOPPO(_PPOBase):
         dual ascent + s-reduction run in ONE dinno_dual_threg launch
         and each primal step is ONE fused penalty-Adam launch (the
         analytic consensus-penalty gradient folds into the update).
-        Rollouts and pred-loss autograd stay per-node torch (the env
-        stepping is host-side by construction)."""
+        The pred-loss gradient comes from ``_grad_stack``. With
+        ``grad_engine: "torch"`` it is per-node autograd, and theta is
+        copied back into the modules after every primal step so the
+        next autograd sees it. With ``"stacked"`` it is
+        ``StackedPPOEngine.grads``: theta stays on the device for all
+        primal iterations (grads, fused_step, nothing in between) and
+        reaches the modules once, at the end of the round. Rollouts are
+        host-side env stepping with either engine."""
         from ..ops import get_ext
 
         ext = get_ext()
         pr = self.pr
-        dt = torch.get_default_dtype()
-        ths = torch.stack(
-            [pr.node_vector(i).detach() for i in range(pr.N)]
-        ).contiguous()
+        self._begin_round()
+        ths = self._theta_stack()
         if getattr(self, "_duals_t", None) is None:
             self._duals_t = torch.zeros_like(ths)
             self._s_t = torch.empty_like(ths)
@@ -205,22 +289,7 @@ class DiNNOPPO(_PPOBase):
             self.duals[i] = self._duals_t[i]
         theta = ths.clone()
         for pit in range(self.pits):
-            grads = []
-            for i in range(pr.N):
-                for p in pr.node_parameters(i):
-                    p.grad = None
-                pred_loss = pr.local_batch_loss(i)
-                pred_loss.backward()
-                grads.append(
-                    torch.cat(
-                        [
-                            (p.grad if p.grad is not None
-                             else torch.zeros_like(p)).reshape(-1)
-                            for p in pr.node_parameters(i)
-                        ]
-                    )
-                )
-            grad = torch.stack(grads).to(dt).contiguous()
+            grad = self._grad_stack(theta)
             # fresh Adam per round (reference recreates the optimizer):
             # first_step resets the moments, step_t restarts at 1
             ext.fused_step(
@@ -229,14 +298,17 @@ class DiNNOPPO(_PPOBase):
                 self.rho, lr, 0.9, 0.999, 1e-8, 0.0,
                 pit + 1, 0, pit == 0, 1, False,
             )
-            for i in range(pr.N):
-                pr.set_node_vector(i, theta[i])
+            if self.engine is None:
+                for i in range(pr.N):
+                    pr.set_node_vector(i, theta[i])
+        if self.engine is not None:
+            self._write_back(theta)
 
     def step_round(self, it):
         pr = self.pr
         self.rho *= self.rho_scaling
         lr = float(self.lr[min(it, len(self.lr) - 1)])
-        if self._hip_available():
+        if self.engine is not None or self._hip_available():
             return self._step_round_hip(it, lr)
         ths = self._snapshot_vectors()
         for i in range(pr.N):
@@ -278,19 +350,19 @@ class DSGDPPO(_PPOBase):
         pr = self.pr
         W = graph_generation.get_metropolis(pr.graph).to(self.device)
         self.alph = self.alph * (1 - self.mu * self.alph)
+        self._begin_round()
         ths = self._snapshot_vectors()
+        rows = []
         for i in range(pr.N):
             mixed = W[i, i] * ths[i]
             for j in self._neighbors(i):
                 mixed = mixed + W[i, j] * ths[j]
-            pr.set_node_vector(i, mixed)
-        for i in range(pr.N):
-            loss = pr.local_batch_loss(i)
-            loss.backward()
-            with torch.no_grad():
-                for p in pr.node_parameters(i):
-                    p.add_(p.grad, alpha=-self.alph)
-                    p.grad.zero_()
+            if self.engine is None:
+                pr.set_node_vector(i, mixed)
+            rows.append(mixed)
+        theta = torch.stack(rows).contiguous()
+        grad = self._grad_stack(theta)
+        self._write_back(theta.add(grad, alpha=-self.alph))
 
 
 class DSGTPPO(_PPOBase):
@@ -319,34 +391,25 @@ class DSGTPPO(_PPOBase):
         }
         self._bootstrapped = False
 
-    def _grad_vector(self, i):
-        pr = self.pr
-        loss = pr.local_batch_loss(i)
-        loss.backward()
-        gs = []
-        with torch.no_grad():
-            for p in pr.node_parameters(i):
-                gs.append(p.grad.reshape(-1).clone())
-                p.grad.zero_()
-        return torch.cat(gs)
-
     def step_round(self, it):
         from ..utils import graph_generation
 
         pr = self.pr
+        self._begin_round()
         if not self._bootstrapped:
             # reference dsgtPPO.py:58-85 bootstraps y, g from the
             # first rollout's gradients
+            grad = self._grad_stack(self._theta_stack())
             for i in range(pr.N):
-                g = self._grad_vector(i)
-                self.y[i] = g.clone()
-                self.g[i] = g.clone()
+                self.y[i] = grad[i].clone()
+                self.g[i] = grad[i].clone()
             self._bootstrapped = True
 
         W = graph_generation.get_metropolis(pr.graph).to(self.device)
         ths = self._snapshot_vectors()
         ys = {i: self.y[i].clone() for i in range(pr.N)}
         y_new = {}
+        rows = []
         for i in range(pr.N):
             p_mix = W[i, i] * (ths[i] - self.alpha_vec * ys[i])
             y_mix = W[i, i] * ys[i]
@@ -355,10 +418,15 @@ class DSGTPPO(_PPOBase):
                     ths[j] - self.alpha_vec * ys[j]
                 )
                 y_mix = y_mix + W[i, j] * ys[j]
-            pr.set_node_vector(i, p_mix)
+            rows.append(p_mix)
             y_new[i] = y_mix
+        theta = torch.stack(rows).contiguous()
+        # the mixed parameters are the round's result; "torch" needs
+        # them in the modules before its autograd as well
+        self._write_back(theta)
+        grad = self._grad_stack(theta)
         for i in range(pr.N):
-            g_next = self._grad_vector(i)
+            g_next = grad[i].clone()
             self.y[i] = y_new[i] + g_next - self.g[i]
             self.g[i] = g_next
 

@@ -54,11 +54,17 @@ def main(argv=None):
     p.add_argument("--max-timesteps", type=int, default=None)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--out", default="./trained")
+    p.add_argument(
+        "--grad-engine", default="torch", choices=["torch", "stacked"],
+        help="PPO gradients by per-node autograd (torch) or batched "
+             "over all nodes on the HIP kernels (stacked; needs a GPU)",
+    )
     args = p.parse_args(argv)
 
     torch.manual_seed(args.seed)
     conf = default_conf(args.alg)
     conf["output_dir"] = args.out
+    conf["grad_engine"] = args.grad_engine
     if args.max_timesteps:
         conf["max_rl_timesteps"] = args.max_timesteps
 

@@ -13,6 +13,8 @@
 
 #include <ATen/hip/HIPContext.h>
 
+#include <map>
+
 namespace {
 
 inline hipStream_t cur_stream() {
@@ -887,7 +889,76 @@ void dw_conv_bwd_idx(torch::Tensor dZ, torch::Tensor X,
   HIP_CHECK_LAST();
 }
 
-// the fc_block_k launch alone (fc1 dW/db are the caller's)
+// fc_fwd_split_k's workspace: per device the partial-z1 slabs
+// [tiles, S, 16, 64] and one int32 ticket per row tile. Owned here so
+// the Python-visible calls need no extra argument and no per-call
+// memset: the tickets are zero when allocated and every launch's
+// reducer blocks leave them zero again. Grown on demand, never freed
+// (torch tensors must not be destroyed after the runtime at exit).
+struct FcSplitWs {
+  torch::Tensor slabs, tickets;
+};
+
+FcSplitWs& fc_split_ws(const torch::Tensor& like, long slab_elems,
+                       long tiles) {
+  static auto* ws = new std::map<int, FcSplitWs>();
+  FcSplitWs& w = (*ws)[like.get_device()];
+  const long need = slab_elems * (long)like.element_size();
+  if (!w.slabs.defined() || w.slabs.numel() < need) {
+    w.slabs = torch::empty(
+        {need}, like.options().dtype(torch::kUInt8));
+  }
+  if (!w.tickets.defined() || w.tickets.numel() < tiles) {
+    w.tickets = torch::zeros(
+        {tiles}, like.options().dtype(torch::kInt32));
+  }
+  return w;
+}
+
+// K slices per row tile of fc_fwd_split_k. 4 puts 128 blocks of 27
+// MFMA k-steps on the chip at the MNIST shape (profiles/README.md has
+// the sweep); NDTA_FC_SPLIT_S overrides it for such sweeps. Wide
+// layers get more slices so that a slice's operand image fits LDS.
+inline long fc_split_slices(long I, long elem_size) {
+  static const long s_env = []() {
+    const char* e = getenv("NDTA_FC_SPLIT_S");
+    const long v = e ? atol(e) : 0;
+    return v >= 1 && v <= 64 ? v : 4;
+  }();
+  const long lds_cap = 160 * 1024;
+  const long ksteps = (I + 3) / 4;
+  long S = s_env;
+  while (fmnist::fc_split_lds_elems(4 * (int)((ksteps + S - 1) / S)) *
+             elem_size > lds_cap) {
+    ++S;
+  }
+  return S;
+}
+
+// Which kernels the fc block runs on. This is the only place the
+// threshold is written. Split: fc_fwd_split_k + fc_dx0_k, while the
+// split forward's grid (row tiles x slices, one block per CU: its
+// operand image is ~100 KB of LDS) fits the chip in one wave of blocks.
+// Past that the blocks queue behind each other and the one-launch
+// fc_block_k, which already has a block for every other CU there, is
+// faster: at 32 nodes x 64 rows (128 tiles, 512 split blocks) the
+// split measured 4.9k rounds/s against 5.7k (profiles/README.md).
+// NDTA_FC_SPLIT=0/1 forces one or the other for A/B runs.
+enum class FcKernel { Split, OneLaunch };
+
+inline FcKernel fc_kernel_for(long tiles, long S) {
+  static const int force = []() {
+    const char* e = getenv("NDTA_FC_SPLIT");
+    return e ? (e[0] == '0' ? 0 : 1) : -1;
+  }();
+  if (force >= 0) return force ? FcKernel::Split : FcKernel::OneLaunch;
+  return tiles * S <= 256 ? FcKernel::Split : FcKernel::OneLaunch;
+}
+
+// the fc block without fc1 dW/db (those are the caller's). Split: the
+// split-K fc1 forward whose last-arriving slice block runs the fc2
+// forward, the loss and the fc2 backward, then dX0 as a grid of its
+// own. OneLaunch: fc_block_k.
 void fc_block_launch(torch::Tensor x0, torch::Tensor theta,
                      torch::Tensor Y_all, torch::Tensor idx,
                      long idx_stride, long idx_off, torch::Tensor grad,
@@ -900,24 +971,55 @@ void fc_block_launch(torch::Tensor x0, torch::Tensor theta,
   CHECK_DEV(dz1g);
   const long L = theta.size(0), n = theta.size(1);
   const long maxlen = Y_all.size(1);
-  TORCH_CHECK(H <= 64 && C <= 16, "fc_block: H <= 64, C <= 16");
+  TORCH_CHECK(H >= 1 && H <= 64 && C >= 1 && C <= 16 && I >= 1 &&
+              M >= 1, "fc_block: 1 <= H <= 64, 1 <= C <= 16");
   const long mtiles = (M + fmnist::FC_RT - 1) / fmnist::FC_RT;
+  const long tiles = mtiles * L;
+  const long S = fc_split_slices(I, x0.element_size());
+  const long KS = 4 * (((I + 3) / 4 + S - 1) / S);
+  const long KSP = fmnist::fc_split_ksp((int)KS);
+  if (fc_kernel_for(tiles, S) == FcKernel::OneLaunch) {
+    DISPATCH_FT(x0, {
+      hipLaunchKernelGGL(fmnist::fc_block_k<scalar_t>,
+          dim3(mtiles, 1, L), dim3(512), 0, cur_stream(),
+          x0.data_ptr<scalar_t>(), theta.data_ptr<scalar_t>(),
+          Y_all.data_ptr<long>(), idx.data_ptr<long>(), idx_stride,
+          idx_off, maxlen, grad.data_ptr<scalar_t>(),
+          dx0.data_ptr<scalar_t>(), dz1g.data_ptr<scalar_t>(),
+          opt_ptr<scalar_t>(loss),
+          n, w1_off, b1_off, w2_off, b2_off, (int)M, (int)I, (int)H,
+          (int)C, (scalar_t)loss_scale, mask_dx0 ? 1 : 0);
+    });
+    HIP_CHECK_LAST();
+    return;
+  }
+  FcSplitWs& ws = fc_split_ws(x0, tiles * S * fmnist::FC_RT * 64, tiles);
   DISPATCH_FT(x0, {
-    hipLaunchKernelGGL(fmnist::fc_block_k<scalar_t>,
-        dim3(mtiles, 1, L), dim3(512), 0, cur_stream(),
+    const size_t shmem =
+        fmnist::fc_split_lds_elems((int)KS) * sizeof(scalar_t);
+    hipLaunchKernelGGL(fmnist::fc_fwd_split_k<scalar_t>,
+        dim3(tiles * S), dim3(256), shmem, cur_stream(),
         x0.data_ptr<scalar_t>(), theta.data_ptr<scalar_t>(),
         Y_all.data_ptr<long>(), idx.data_ptr<long>(), idx_stride,
         idx_off, maxlen, grad.data_ptr<scalar_t>(),
-        dx0.data_ptr<scalar_t>(), dz1g.data_ptr<scalar_t>(),
-        opt_ptr<scalar_t>(loss),
+        dz1g.data_ptr<scalar_t>(), opt_ptr<scalar_t>(loss),
+        reinterpret_cast<scalar_t*>(ws.slabs.data_ptr()),
+        ws.tickets.data_ptr<int>(),
         n, w1_off, b1_off, w2_off, b2_off, (int)M, (int)I, (int)H,
-        (int)C, (scalar_t)loss_scale, mask_dx0 ? 1 : 0);
+        (int)C, (scalar_t)loss_scale, (int)mtiles, (int)S, (int)KS,
+        (int)KSP);
+    hipLaunchKernelGGL(fmnist::fc_dx0_k<scalar_t>,
+        dim3((I + 15) / 16, (M + 63) / 64, L), dim3(256), 0,
+        cur_stream(),
+        x0.data_ptr<scalar_t>(), theta.data_ptr<scalar_t>(),
+        dz1g.data_ptr<scalar_t>(), dx0.data_ptr<scalar_t>(),
+        n, w1_off, (int)M, (int)I, (int)H, mask_dx0 ? 1 : 0);
   });
   HIP_CHECK_LAST();
 }
 
-// one-launch fc block: fc1+fc2 fwd, NLL, full fc backward (see
-// fused_mnist.hip fc_block_k). Caller pre-zeroes the grad stack.
+// the fc block: fc1+fc2 fwd, NLL, full fc backward (see fused_mnist.hip
+// fc_fwd_split_k, fc_dx0_k). Caller pre-zeroes the grad stack.
 void fc_block(torch::Tensor x0, torch::Tensor theta,
               torch::Tensor Y_all, torch::Tensor idx, long idx_stride,
               long idx_off, torch::Tensor grad, torch::Tensor dx0,
@@ -934,10 +1036,11 @@ void fc_block(torch::Tensor x0, torch::Tensor theta,
 }
 
 // One native call per forward+backward of the conv -> fc1 -> fc2 -> NLL
-// model on the index-sourced path: conv forward, the fc block, then
-// the merged fc1-dW + conv-backward launch, all on the current stream.
-// At ~10 us of host time per pybind call the three separate calls no
-// longer hid under the iteration's GPU time. Caller pre-zeroes the
+// model on the index-sourced path: conv forward, the fc block's two
+// launches (split-K forward + tail, dX0), then the merged fc1-dW +
+// conv-backward launch, all on the current stream. At ~10 us of host
+// time per pybind call, separate calls no longer hid under the
+// iteration's GPU time. Caller pre-zeroes the
 // grad stack (and the loss slot).
 void mnist_fwd_bwd(torch::Tensor X_all, torch::Tensor src_idx,
                    long idx_stride, long idx_off, torch::Tensor theta,

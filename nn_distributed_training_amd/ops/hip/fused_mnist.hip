@@ -331,21 +331,29 @@ __global__ __launch_bounds__(256) void mnist_train_step_k(
 
 
 // ---------------------------------------------------------------------
-// Fused fc BLOCK (round 2): fc1+ReLU -> fc2 logits -> log-softmax+NLL
-// -> fc2 dW/db -> dz1 -> fc1 dW/db -> dX0, ONE launch per primal
-// iteration (replaces 7 small kernels: 2x linear_fwd, nll_fused,
-// 2x linear_bwd_dw, 2x linear_bwd_dx — each near the ~5 us kernel
-// floor, ~65 us/iteration of GPU time at the MNIST bench shapes,
+// Fused fc BLOCK: fc1+ReLU -> fc2 logits -> log-softmax+NLL -> fc2
+// dW/db -> dz1 -> dX0 (replaces 7 small kernels: 2x linear_fwd,
+// nll_fused, 2x linear_bwd_dw, 2x linear_bwd_dx — each near the ~5 us
+// kernel floor, ~65 us/iteration of GPU time at the MNIST bench shapes,
 // profiles/mnist_r2d_topk.txt). The conv layer stays separate (its
-// kernels are not floor-bound).
+// kernels are not floor-bound); fc1 dW/db run on the store-path dw
+// kernel from the exported dz1.
 //
-// The three big contractions run on the f64/f32 MFMA matrix cores
-// (VERDICT r1 #2): fc1 fwd (K = I), fc1 dW (K = RT rows), dX0
-// (K = H), with y1 and dz1 LDS-resident — y1 never touches HBM.
-// One block = RT(16) rows of one node; grid (ceil(M/RT), 1, L).
-// Requires H <= 64, C <= 16; fc grad slices accumulate atomically
-// (caller zeroes the whole grad stack).
+// The big contractions run on the f64/f32 MFMA matrix cores: fc1 fwd
+// (K = I) and dX0 (K = H); y1 is LDS-resident and never touches HBM.
+// A row tile is RT(16) rows of one node. Requires H <= 64, C <= 16;
+// the fc2 grad slices accumulate atomically (caller zeroes the whole
+// grad stack).
+//
+// Two chip-filling launches. As one launch of one block per row tile
+// this was 32 blocks at the MNIST shape (8 nodes x 64 rows): each
+// pulled all of W1 through one CU for the fc1 forward and again for
+// dX0 while 7/8 of the chip idled. Here the fc1 forward is split over K
+// (fc_fwd_split_k: row tiles x S slices, the last slice block to
+// arrive runs the tail) and dX0 is a grid of its own (fc_dx0_k: one
+// block per 16-column strip of I). No block ever waits for another.
 constexpr int FC_RT = 16;
+constexpr int FC_W2S = 65;  // padded LDS row stride of W2
 
 // Diagnostic phase clock (compiled out unless the extension is built
 // with NDTA_BUILD_DEFINES=-DNDTA_FC_PHASE_CLOCK): thread 0 of each
@@ -368,8 +376,9 @@ __device__ unsigned long long fc_phase_stamps[FC_CLK_BLOCKS * 8];
 #else
 #define FC_STAMP(slot) do {} while (0)
 #endif
-constexpr int FC_W2S = 65;  // padded LDS row stride of W2
-
+// fc_block_k: the whole block as ONE launch, one 512-thread block per
+// row tile. Kept for stacks with so many row tiles that the split
+// forward's grid would pass the CU count (ext.hip fc_kernel_for).
 // one 16-column strip of the dX0 pass: W1[0:64, ix:ix+16] as 16 MFMA B
 // operands plus the x0 values that carry the conv relu' mask for the
 // lane's four output elements
@@ -698,10 +707,394 @@ __global__ __launch_bounds__(512) void fc_block_k(
 #endif
 }
 
+//
+// fc_fwd_split_k LDS arena (one dynamic array): the fixed tail arenas
+// first, then the [80][KSP] operand image: rows 0-15 the x0 tile slice,
+// rows 16-79 the W1 slice, both row-major in k exactly as they sit in
+// memory, so staging is 16-byte loads and 16-byte LDS stores. KSP = 2
+// (mod 32) keeps the MFMA fragment reads (16 rows x 4 k per wave) off
+// each other's banks in fp64 and fp32.
+constexpr int FCS_W2 = 0;                          // [17][65] W2 | b2
+constexpr int FCS_Y1 = FCS_W2 + 17 * FC_W2S;       // [16][65]
+constexpr int FCS_DZ2 = FCS_Y1 + FC_RT * 65;       // [16][17]
+constexpr int FCS_FLAG = FCS_DZ2 + FC_RT * 17;     // "I am last" word
+constexpr int FCS_STG = 2424;                      // 16-byte multiple
+static_assert(FCS_FLAG + 2 <= FCS_STG, "fc split arena overlap");
+constexpr int FCS_ROWS = FC_RT + 64;               // image rows
+constexpr int FCS_NLD = 18;  // staging loads in flight per thread
+
+// padded row length of the operand image for a KS-wide slice
+inline int fc_split_ksp(int KS) {
+  return KS + ((2 - KS % 32) + 32) % 32;
+}
+
+// elements of dynamic LDS fc_fwd_split_k needs for a KS-wide slice
+inline long fc_split_lds_elems(int KS) {
+  return FCS_STG + (long)FCS_ROWS * fc_split_ksp(KS);
+}
+
+// A slab word crosses from its slice block to the tile's reducer inside
+// one launch. Relaxed agent-scope atomic accesses of the word's bits
+// are the write-through store and the L1-bypassing load that such a
+// hand-off needs (the .s shows both with the sc1 bit).
+template <typename T>
+struct slab_bits { using type = unsigned long long; };
+template <>
+struct slab_bits<float> { using type = unsigned; };
+
+template <typename T>
+DEV_INLINE void slab_store(T* p, T v) {
+  using U = typename slab_bits<T>::type;
+  __hip_atomic_store(reinterpret_cast<U*>(p), __builtin_bit_cast(U, v),
+                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <typename T>
+DEV_INLINE T slab_load(const T* p) {
+  using U = typename slab_bits<T>::type;
+  return __builtin_bit_cast(
+      T, __hip_atomic_load(reinterpret_cast<const U*>(p),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void fc_fwd_split_k(
+    const T* __restrict__ x0,        // [L*M, I] conv/pool output
+    const T* __restrict__ theta,     // [L, n]
+    const long* __restrict__ Y_all,  // [L, maxlen] targets
+    const long* __restrict__ idx,    // index stream
+    long idx_stride, long idx_off, long maxlen,
+    T* __restrict__ grad,            // [L, n]
+    T* __restrict__ dz1g,            // [L*M, H] dz1 out
+    T* __restrict__ loss,            // nullable [L]
+    T* slabs,                        // [tiles, S, 16, 64] partial z1
+    int* tickets,                    // [tiles], zero between launches
+    long n, long w1_off, long b1_off, long w2_off, long b2_off,
+    int M, int I, int H, int C, T loss_scale, int mtiles, int S, int KS,
+    int KSP) {
+  using MF = gmfma::mfma_t<T>;
+  using acc_t = typename MF::acc_t;
+  typedef T vec2 __attribute__((ext_vector_type(2)));
+  constexpr int RT = FC_RT;
+  extern __shared__ __align__(16) unsigned char fcs_raw[];
+  T* lds = reinterpret_cast<T*>(fcs_raw);
+  T* w2s = lds + FCS_W2;
+  T* y1s = lds + FCS_Y1;
+  T* dz2s = lds + FCS_DZ2;
+  int* lastf = reinterpret_cast<int*>(lds + FCS_FLAG);
+  T* stg = lds + FCS_STG;
+
+  const int tile = blockIdx.x / S;
+  const int slice = blockIdx.x - tile * S;
+  const long l = tile / mtiles;
+  const int m0 = (tile - (int)l * mtiles) * RT;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int lo = lane & 15;
+  const int lk = lane >> 4;
+  const T* th = theta + l * n;
+  const T* W1 = th + w1_off;
+  const T* x0b = x0 + (long)(l * (long)M + m0) * I;
+  const int kb = slice * KS;
+  const int klen = min(KS, I - kb);  // <= 0: an empty slice
+
+  // what only the reducer's tail needs still loads in every block, in
+  // the staging round trip and clamped not branched, so that the tail
+  // starts no load chain of its own: the row's index-stream entry (its
+  // target is fetched below, once this has landed), W2, b2 and b1
+  const long trow =
+      idx[l * idx_stride + idx_off + min(m0 + (tid >> 4), M - 1)];
+  T w2v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    w2v[j] = th[w2_off + min(tid + j * 256, C * H - 1)];
+  }
+  const T b2v = th[b2_off + min(tid, C - 1)];
+  const T b1v = th[b1_off + min(tid & 63, H - 1)];
+
+  if (klen == KS && m0 + RT <= M && H == 64) {
+    // full slice: guard-free 16-byte loads, FCS_NLD per thread in
+    // flight, then 16-byte LDS stores. (row, kp) walk the image in
+    // steps of 256 pairs without a division per load.
+    const int kph = KS / 2;
+    const int dq = 256 / kph, dr = 256 - dq * kph;
+    int row = tid / kph, kp = tid - row * kph;
+    while (row < FCS_ROWS) {
+      vec2 v[FCS_NLD];
+      int dst[FCS_NLD];
+#pragma unroll
+      for (int j = 0; j < FCS_NLD; ++j) {
+        const int rc = min(row, FCS_ROWS - 1);
+        const T* src = rc < RT ? x0b + (long)rc * I
+                               : W1 + (long)(rc - RT) * I;
+        v[j] = *reinterpret_cast<const vec2*>(src + kb + 2 * kp);
+        dst[j] = row < FCS_ROWS ? rc * KSP + 2 * kp : -1;
+        kp += dr;
+        row += dq;
+        if (kp >= kph) { kp -= kph; ++row; }
+      }
+#pragma unroll
+      for (int j = 0; j < FCS_NLD; ++j) {
+        if (dst[j] >= 0) *reinterpret_cast<vec2*>(stg + dst[j]) = v[j];
+      }
+    }
+  } else {
+    // K tail, M tail, H < 64 or an empty slice: guarded scalar loads,
+    // zeros where the slice, the row tile or W1 ends
+    for (int u = tid; u < FCS_ROWS * KS; u += 256) {
+      const int r = u / KS, k = u - r * KS;
+      T v = T(0);
+      if (k < klen) {
+        if (r < RT) {
+          if (m0 + r < M) v = x0b[(long)r * I + kb + k];
+        } else if (r - RT < H) {
+          v = W1[(long)(r - RT) * I + kb + k];
+        }
+      }
+      stg[r * KSP + k] = v;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int t = tid + j * 256;
+    if (t < C * H) w2s[(t / H) * FC_W2S + t % H] = w2v[j];
+  }
+  if (tid < C) w2s[16 * FC_W2S + tid] = b2v;
+  const int tgt = (int)Y_all[l * maxlen + trow];
+  __syncthreads();
+
+  // this slice's share of z1: wave w owns o-fragment [16w, 16w+16);
+  // two accumulators halve the MFMA dependency chain
+  {
+    acc_t a0 = {}, a1 = {};
+    const T* Ar = stg + lo * KSP + lk;
+    const T* Br = stg + (RT + wid * 16 + lo) * KSP + lk;
+    int kk = 0;
+#pragma unroll 4
+    for (; kk + 8 <= KS; kk += 8) {
+      a0 = MF::mma(Ar[kk], Br[kk], a0);
+      a1 = MF::mma(Ar[kk + 4], Br[kk + 4], a1);
+    }
+    if (kk < KS) a0 = MF::mma(Ar[kk], Br[kk], a0);
+    T* slab = slabs + ((long)tile * S + slice) * (RT * 64);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      slab_store(&slab[MF::acc_row(lane, r) * 64 + wid * 16 + lo],
+                 a0[r] + a1[r]);
+    }
+  }
+
+  // publish the slab and draw a ticket. The slab went out write-through
+  // (slab_store), so there is no release fence: every wave drains its
+  // stores, the block meets, one lane adds to the tile's ticket. The
+  // block that draws S - 1 is the reducer, the only one to touch the
+  // ticket again, and reads every slab word past its L1 (slab_load), so
+  // it needs no acquire either; the wavefront fence only keeps the
+  // compiler from moving those loads up.
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    const int got = __hip_atomic_fetch_add(
+        &tickets[tile], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = got == S - 1;
+    if (last) {
+      __hip_atomic_store(&tickets[tile], 0, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    }
+    *lastf = last;
+  }
+  __syncthreads();
+  if (!*lastf) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  // reducer: z1 = slabs summed in slice order (independent of arrival
+  // order), y1 = relu(z1 + b1) into LDS (never stored to HBM)
+  {
+    const T* sl = slabs + (long)tile * S * (RT * 64);
+    T z[4] = {};
+    for (int s0 = 0; s0 < S; s0 += 4) {  // 16 loads in flight, clamped
+      T v[4][4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const long so = (long)min(s0 + q, S - 1) * (RT * 64) + tid;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[q][j] = slab_load(&sl[so + j * 256]);
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (s0 + q < S) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) z[j] += v[q][j];
+        }
+      }
+    }
+    const int o = tid & 63;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int m = (tid >> 6) + 4 * j;
+      const T v = z[j] + b1v;
+      y1s[m * 65 + o] = (o < H && v > T(0)) ? v : T(0);
+    }
+  }
+  __syncthreads();
+
+  // P2: fc2 logits + log-softmax + NLL dZ2, one (row, class) per
+  // thread: row m's classes sit in 16 adjacent lanes, so the row max
+  // and the row sum are 4 xor-shuffles each and every exp runs once.
+  {
+    const int m = tid >> 4, c = tid & 15;
+    const bool act = c < C;
+    const bool rowok = (m0 + m) < M;
+    T z = -INFINITY;
+    if (act) {
+      z = w2s[16 * FC_W2S + c];  // b2
+      if (H == 64) {  // 8 partial sums so the LDS loads batch
+        T part[8] = {};
+#pragma unroll
+        for (int hq = 0; hq < 8; ++hq) {
+#pragma unroll
+          for (int hh = 0; hh < 8; ++hh) {
+            const int h = hq * 8 + hh;
+            part[hh] += y1s[m * 65 + h] * w2s[c * FC_W2S + h];
+          }
+        }
+#pragma unroll
+        for (int hh = 0; hh < 8; ++hh) z += part[hh];
+      } else {
+        for (int h = 0; h < H; ++h) {
+          z += y1s[m * 65 + h] * w2s[c * FC_W2S + h];
+        }
+      }
+    }
+    T mx = z;
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) {
+      const T o = __shfl_xor(mx, off, 16);
+      mx = o > mx ? o : mx;
+    }
+    const T e = act ? ::exp(z - mx) : T(0);
+    T sum = e;
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) {
+      sum += __shfl_xor(sum, off, 16);
+    }
+    if (act) {
+      T dz = T(0);
+      if (rowok) {
+        dz = (e / sum - (c == tgt ? T(1) : T(0))) *
+             (loss_scale / T(M));
+        if (c == tgt && loss != nullptr) {
+          const T lse = mx + ::log(sum);
+          atomicAdd(&loss[l], -(z - lse) / T(M));
+        }
+      }
+      dz2s[m * 17 + c] = dz;
+    }
+  }
+  __syncthreads();
+
+  // P3: dz1 = (dz2 @ W2) * relu'(y1) -> global (fc_dx0_k and the fc1
+  // dW/db kernel read it); fc2 dW/db
+  for (int t = tid; t < RT * H; t += 256) {
+    const int m = t / H, h = t % H;
+    T s = T(0);
+    for (int c = 0; c < C; ++c) {
+      s += dz2s[m * 17 + c] * w2s[c * FC_W2S + h];
+    }
+    if (m0 + m < M) {
+      dz1g[(long)(l * (long)M + m0 + m) * H + h] =
+          y1s[m * 65 + h] > T(0) ? s : T(0);
+    }
+  }
+  for (int t = tid; t < C * H; t += 256) {
+    const int c = t / H, h = t % H;
+    T s = T(0);
+    for (int m = 0; m < RT; ++m) {
+      s += dz2s[m * 17 + c] * y1s[m * 65 + h];
+    }
+    atomicAdd(&grad[l * n + w2_off + c * H + h], s);
+  }
+  if (tid >= 32 && tid < 32 + C) {
+    const int c = tid - 32;
+    T s = T(0);
+    for (int m = 0; m < RT; ++m) s += dz2s[m * 17 + c];
+    atomicAdd(&grad[l * n + b2_off + c], s);
+  }
+}
+
+// dX0 = dz1 @ W1 with the conv relu' mask, one block per (16-column
+// strip of I, 64-row group of M, node): wave w takes rows [16w, 16w+16)
+// of the group. A lane's operands are 16 dz1 values (A), 16 W1 values
+// (B) and the 4 x0 values that carry the mask: 36 independent loads
+// issued together, clamped rather than branched at the M/I/H tails (a
+// clamped load reads valid memory and its value is replaced by 0), so
+// the kernel is one load round trip, 16 MFMAs and a masked store, with
+// no LDS and no barrier.
+template <typename T>
+__global__ __launch_bounds__(256) void fc_dx0_k(
+    const T* __restrict__ x0,     // [L*M, I]
+    const T* __restrict__ theta,  // [L, n]
+    const T* __restrict__ dz1g,   // [L*M, H]
+    T* __restrict__ dx0,          // [L*M, I]
+    long n, long w1_off, int M, int I, int H, int mask_dx0) {
+  using MF = gmfma::mfma_t<T>;
+  using acc_t = typename MF::acc_t;
+  const long l = blockIdx.z;
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int lo = lane & 15;
+  const int lk = lane >> 4;
+  const int m0 = blockIdx.y * 64 + wid * 16;
+  if (m0 >= M) return;  // wave-uniform; the kernel has no barrier
+  const int i = blockIdx.x * 16 + lo;
+  const int ic = min(i, I - 1);
+  const T* W1 = theta + l * n + w1_off;
+  const T* dzr = dz1g + (long)(l * (long)M + min(m0 + lo, M - 1)) * H;
+
+  T a[16], w[16], xm[4];
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
+    const int h = min(4 * t + lk, H - 1);
+    a[t] = dzr[h];
+    w[t] = W1[(long)h * I + ic];
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int m = min(m0 + MF::acc_row(lane, r), M - 1);
+    xm[r] = mask_dx0 ? x0[(long)(l * (long)M + m) * I + ic] : T(1);
+  }
+  // zero what the clamps stood in for: rows past M, columns past I and
+  // the H < 64 padding of the contraction
+  const bool aok = m0 + lo < M;
+  const bool wok = i < I;
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
+    const bool hok = 4 * t + lk < H;
+    a[t] = (aok && hok) ? a[t] : T(0);
+    w[t] = (wok && hok) ? w[t] : T(0);
+  }
+  acc_t ax0 = {}, ax1 = {};
+#pragma unroll
+  for (int t = 0; t < 16; t += 2) {
+    ax0 = MF::mma(a[t], w[t], ax0);
+    ax1 = MF::mma(a[t + 1], w[t + 1], ax1);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int m = m0 + MF::acc_row(lane, r);
+    if (m < M && i < I) {
+      // conv relu' mask: x0 IS the conv block's relu output
+      dx0[(long)(l * (long)M + m) * I + i] =
+          xm[r] > T(0) ? ax0[r] + ax1[r] : T(0);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------
 // Merged backward launch: fc1 dW/db (gemm::linear_bwd_dw_body) and the
 // gather-sourced conv dW/db (conv::conv_pool_bwd_body) as two roles of
-// one flat grid of 256-thread blocks. Both only read what fc_block_k
+// one flat grid of 256-thread blocks. Both only read what the fc block
 // produced (dz1 + x0 for one, dx0 + the pool argmax for the other) and
 // write disjoint slices of the grad stack, so as separate launches the
 // 7.8 us dW kernel sat in a serial slot of its own; in one grid the 864

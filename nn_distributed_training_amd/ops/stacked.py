@@ -618,7 +618,7 @@ class StackedEngine:
 
     # ------------------------------------------------------------------
     def fc_block_applicable(self):
-        """One-launch fused fc block (fused_mnist.hip fc_block_k):
+        """Fused fc block (fused_mnist.hip fc_fwd_split_k + fc_dx0_k):
         conv -> [fc1+fc2 fwd + NLL + full fc bwd] -> conv bwd.
         Replaces 7 floor-bound small kernels per primal iteration
         (~65 us -> ~15 us of GPU time at the MNIST bench shapes)."""
@@ -630,7 +630,7 @@ class StackedEngine:
             and self.classification
             and len(ls) == 3
             and ls[0].kind == "conv_pool"
-            # dX0 carries the conv block's relu' mask inside fc_block_k
+            # dX0 carries the conv block's relu' mask inside fc_dx0_k
             and getattr(ls[0], "activation", "relu") == "relu"
             and ls[1].kind == "linear"
             and ls[2].kind == "linear"

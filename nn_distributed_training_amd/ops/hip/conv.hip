@@ -256,6 +256,13 @@ constexpr int pow2_at_least(int x) {
   return p;
 }
 
+// defined after conv_pool_bwd_body, whose end it is
+template <typename T, int KMAX>
+DEV_INLINE void conv_bwd_reduce_tail(
+    T (&acc)[pow2_at_least(KMAX * KMAX + 1)], T* __restrict__ gstack,
+    long n, long w_off, long b_off, int l, int f, int K, int tid,
+    int nthr, T* __restrict__ red);
+
 // Backward to weights/bias: route each pooled grad to its argmax conv
 // position, multiply by the image window. dY is the grad AFTER the relu
 // mask (pooled output > 0), applied by the caller via act_grad.
@@ -380,13 +387,27 @@ DEV_INLINE void conv_pool_bwd_body(
     }
   }
 
-  // reduce the K*K+1 partials: one butterfly per wave (no barriers; a
-  // lane without items, a wave without items and a tap skipped because
-  // K < KMAX all carry exact zeros), the lane that ends up with a
-  // slot's wave total parks it in LDS, then ONE barrier and the first
-  // KMAX*KMAX+1 threads finish their tap in parallel. Skipped taps are
-  // neither parked nor added.
-  // red: [tap][wave]
+  conv_bwd_reduce_tail<T, KMAX>(acc, gstack, n, w_off, b_off, l, f, K,
+                                tid, nthr, red);
+}
+
+// The end of a conv-backward block: acc[0..KMAX*KMAX) are the thread's
+// dW tap partials (KMAX-strided), acc[KMAX*KMAX] its db partial, all for
+// filter f of node l.
+// Reduce the K*K+1 partials: one butterfly per wave (no barriers; a
+// lane without items, a wave without items and a tap skipped because
+// K < KMAX all carry exact zeros), the lane that ends up with a
+// slot's wave total parks it in LDS, then ONE barrier and the first
+// KMAX*KMAX+1 threads finish their tap in parallel. Skipped taps are
+// neither parked nor added. Every thread of the block must arrive.
+// red: [tap][wave]
+template <typename T, int KMAX>
+DEV_INLINE void conv_bwd_reduce_tail(
+    T (&acc)[pow2_at_least(KMAX * KMAX + 1)], T* __restrict__ gstack,
+    long n, long w_off, long b_off, int l, int f, int K, int tid,
+    int nthr, T* __restrict__ red) {
+  constexpr int NTAP = KMAX * KMAX;
+  constexpr int NSLOT = pow2_at_least(NTAP + 1);
   const int lane = tid & (WAVE - 1);
   const int wid = tid / WAVE;
   T* wslice = gstack + (long)l * n + w_off + (long)f * K * K;

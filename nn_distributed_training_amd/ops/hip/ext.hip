@@ -958,7 +958,8 @@ inline FcKernel fc_kernel_for(long tiles, long S) {
 // the fc block without fc1 dW/db (those are the caller's). Split: the
 // split-K fc1 forward whose last-arriving slice block runs the fc2
 // forward, the loss and the fc2 backward, then dX0 as a grid of its
-// own. OneLaunch: fc_block_k.
+// own (left out with want_dx0 = false, for a caller whose backward
+// computes dX0 itself). OneLaunch: fc_block_k, which always writes dx0.
 void fc_block_launch(torch::Tensor x0, torch::Tensor theta,
                      torch::Tensor Y_all, torch::Tensor idx,
                      long idx_stride, long idx_off, torch::Tensor grad,
@@ -966,7 +967,7 @@ void fc_block_launch(torch::Tensor x0, torch::Tensor theta,
                      c10::optional<torch::Tensor> loss, long w1_off,
                      long b1_off, long w2_off, long b2_off, long M,
                      long I, long H, long C, double loss_scale,
-                     bool mask_dx0) {
+                     bool mask_dx0, bool want_dx0 = true) {
   CHECK_DEV(x0); CHECK_DEV(theta); CHECK_DEV(grad); CHECK_DEV(dx0);
   CHECK_DEV(dz1g);
   const long L = theta.size(0), n = theta.size(1);
@@ -1008,12 +1009,14 @@ void fc_block_launch(torch::Tensor x0, torch::Tensor theta,
         n, w1_off, b1_off, w2_off, b2_off, (int)M, (int)I, (int)H,
         (int)C, (scalar_t)loss_scale, (int)mtiles, (int)S, (int)KS,
         (int)KSP);
-    hipLaunchKernelGGL(fmnist::fc_dx0_k<scalar_t>,
-        dim3((I + 15) / 16, (M + 63) / 64, L), dim3(256), 0,
-        cur_stream(),
-        x0.data_ptr<scalar_t>(), theta.data_ptr<scalar_t>(),
-        dz1g.data_ptr<scalar_t>(), dx0.data_ptr<scalar_t>(),
-        n, w1_off, (int)M, (int)I, (int)H, mask_dx0 ? 1 : 0);
+    if (want_dx0) {
+      hipLaunchKernelGGL(fmnist::fc_dx0_k<scalar_t>,
+          dim3((I + 15) / 16, (M + 63) / 64, L), dim3(256), 0,
+          cur_stream(),
+          x0.data_ptr<scalar_t>(), theta.data_ptr<scalar_t>(),
+          dz1g.data_ptr<scalar_t>(), dx0.data_ptr<scalar_t>(),
+          n, w1_off, (int)M, (int)I, (int)H, mask_dx0 ? 1 : 0);
+    }
   });
   HIP_CHECK_LAST();
 }
@@ -1035,11 +1038,127 @@ void fc_block(torch::Tensor x0, torch::Tensor theta,
   linear_bwd_dw(dz1g, x0, grad, w1_off, b1_off, M, I, H);
 }
 
+// Whether the backward of the conv -> fc1 model computes dX0 inside the
+// merged launch (fused_mnist.hip dw_dx0_conv_bwd_k) instead of reading
+// it from memory. This is the only place the condition is written: the
+// fc block is on its split path (the one-launch fc_block_k writes dX0
+// anyway), fc1's dW takes the Small kernel (the one the merged launches
+// carry), a 16-column strip of I lies inside one filter, and K is one
+// of the exact tap-loop sizes. NDTA_BWD_DX0=0 keeps the two launches
+// (fc_dx0_k, dw_conv_bwd_k) for A/B runs.
+inline bool bwd_dx0_fused(long L, long M, long I, long H, long F, long K,
+                          long IMG, long elem_size) {
+  static const bool off = []() {
+    const char* e = getenv("NDTA_BWD_DX0");
+    return e && e[0] == '0';
+  }();
+  if (off) return false;
+  const long P = (IMG - (K - 1)) / 2;
+  if (L < 1 || M < 1 || P < 1 || I != F * P * P) return false;
+  const long tiles = (M + fmnist::FC_RT - 1) / fmnist::FC_RT * L;
+  return fc_kernel_for(tiles, fc_split_slices(I, elem_size)) ==
+             FcKernel::Split &&
+         dw_kernel_for(M, I, H) == DwKernel::Small &&
+         (P * P) % 16 == 0 && (K == 5 || K == 7) && H >= 1 && H <= 64;
+}
+
+bool bwd_dx0_fused_for(long L, long M, long I, long H, long F, long K,
+                       long IMG, long elem_size) {
+  return bwd_dx0_fused(L, M, I, H, F, K, IMG, elem_size);
+}
+
+// fc1 dW/db + dX0 + gather-sourced conv dW/db in ONE launch. Caller has
+// checked bwd_dx0_fused.
+void launch_dw_dx0_conv_bwd(
+    const torch::Tensor& dz1, const torch::Tensor& x0,
+    const torch::Tensor& theta, const torch::Tensor& pidx,
+    const torch::Tensor& X_all, const torch::Tensor& src_idx,
+    long idx_stride, long idx_off, const torch::Tensor& gstack,
+    long w1_off, long b1_off, long M, long I, long H, long cw_off,
+    long cb_off, long F, long K, long IMG) {
+  CHECK_DEV(dz1); CHECK_DEV(x0); CHECK_DEV(theta); CHECK_DEV(pidx);
+  CHECK_DEV(X_all); CHECK_DEV(src_idx); CHECK_DEV(gstack);
+  const long L = gstack.size(0), n = gstack.size(1);
+  const long maxlen = X_all.size(1);
+  TORCH_CHECK(theta.size(0) == L && theta.size(1) == n,
+              "theta and gstack must both be [L, n]");
+  TORCH_CHECK(dz1.numel() >= L * M * H && x0.numel() >= L * M * I &&
+                  pidx.numel() >= L * M * I,
+              "dz1 [L*M, H], x0 and pidx [L*M, I] expected");
+  TORCH_CHECK(w1_off >= 0 && w1_off + H * I <= n && b1_off >= 0 &&
+                  b1_off + H <= n && cw_off >= 0 &&
+                  cw_off + F * K * K <= n && cb_off >= 0 &&
+                  cb_off + F <= n, "layer slices must lie inside [0, n)");
+  TORCH_CHECK(X_all.numel() >= L * maxlen * IMG * IMG &&
+                  idx_off >= 0 && idx_off + M <= idx_stride &&
+                  src_idx.numel() >= L * idx_stride,
+              "X_all [L, maxlen, IMG*IMG], src_idx [L, idx_stride]");
+  const long gx = (I + 15) / 16, gy = (H + 15) / 16;
+  const long n_dw = gx * gy * L;
+  const long cv_gx = I / 16, cv_gy = (M + 63) / 64;
+  const long n_cv = cv_gx * cv_gy * L;
+  DISPATCH_FT(dz1, {
+    dispatch_kmax(K, [&](auto kmax) {
+      hipLaunchKernelGGL(
+          (fmnist::dw_dx0_conv_bwd_k<scalar_t, decltype(kmax)::value>),
+          dim3(n_dw + n_cv), dim3(256), 0, cur_stream(),
+          dz1.data_ptr<scalar_t>(), x0.data_ptr<scalar_t>(), w1_off,
+          b1_off, (int)M, (int)I, (int)H, (int)gx, (int)gy,
+          theta.data_ptr<scalar_t>(), pidx.data_ptr<unsigned char>(),
+          X_all.data_ptr<scalar_t>(), cw_off, cb_off, (int)IMG,
+          (int)cv_gx, (int)cv_gy, (int)n_cv, src_idx.data_ptr<long>(),
+          idx_stride, idx_off, maxlen, gstack.data_ptr<scalar_t>(), n);
+    });
+  });
+  HIP_CHECK_LAST();
+}
+
+// The whole backward below the fc block from dz1: fc1 dW/db and conv
+// dW/db, with dX0 = (dz1 @ W1) * relu'(x0) in between. One launch where
+// bwd_dx0_fused says so; elsewhere fc_dx0_k into a scratch dX0, then
+// dw_conv_bwd_idx. The conv slice of gstack is zero on entry.
+void dw_dx0_conv_bwd_idx(torch::Tensor dz1, torch::Tensor x0,
+                         torch::Tensor theta, torch::Tensor pidx,
+                         torch::Tensor X_all, torch::Tensor src_idx,
+                         long idx_stride, long idx_off,
+                         torch::Tensor gstack, long w1_off, long b1_off,
+                         long M, long I, long H, long cw_off,
+                         long cb_off, long F, long K, long IMG) {
+  const long L = gstack.size(0), n = gstack.size(1);
+  if (bwd_dx0_fused(L, M, I, H, F, K, IMG, x0.element_size())) {
+    launch_dw_dx0_conv_bwd(dz1, x0, theta, pidx, X_all, src_idx,
+                           idx_stride, idx_off, gstack, w1_off, b1_off,
+                           M, I, H, cw_off, cb_off, F, K, IMG);
+    return;
+  }
+  CHECK_DEV(dz1); CHECK_DEV(x0); CHECK_DEV(theta);
+  TORCH_CHECK(H >= 1 && H <= 64 && M >= 1 && I >= 1,
+              "dw_dx0_conv_bwd_idx: 1 <= H <= 64");
+  TORCH_CHECK(theta.size(0) == L && theta.size(1) == n &&
+                  dz1.numel() >= L * M * H && x0.numel() >= L * M * I,
+              "theta [L, n], dz1 [L*M, H], x0 [L*M, I] expected");
+  torch::Tensor dx0 = torch::empty_like(x0);
+  DISPATCH_FT(x0, {
+    hipLaunchKernelGGL(fmnist::fc_dx0_k<scalar_t>,
+        dim3((I + 15) / 16, (M + 63) / 64, L), dim3(256), 0,
+        cur_stream(),
+        x0.data_ptr<scalar_t>(), theta.data_ptr<scalar_t>(),
+        dz1.data_ptr<scalar_t>(), dx0.data_ptr<scalar_t>(),
+        n, w1_off, (int)M, (int)I, (int)H, 1);
+  });
+  HIP_CHECK_LAST();
+  dw_conv_bwd_idx(dz1, x0, dx0, pidx, X_all, src_idx, idx_stride,
+                  idx_off, gstack, w1_off, b1_off, M, I, H, cw_off,
+                  cb_off, F, K, IMG);
+}
+
 // One native call per forward+backward of the conv -> fc1 -> fc2 -> NLL
-// model on the index-sourced path: conv forward, the fc block's two
-// launches (split-K forward + tail, dX0), then the merged fc1-dW +
-// conv-backward launch, all on the current stream. At ~10 us of host
-// time per pybind call, separate calls no longer hid under the
+// model on the index-sourced path: conv forward, the fc block (split-K
+// forward + tail), then the merged fc1-dW + dX0 + conv-backward launch:
+// three launches on the current stream, and dx0 is not touched. Where
+// bwd_dx0_fused says no, the fc block writes dx0 (fc_dx0_k or
+// fc_block_k) and dw_conv_bwd_idx reads it, as before. At ~10 us of
+// host time per pybind call, separate calls no longer hid under the
 // iteration's GPU time. Caller pre-zeroes the
 // grad stack (and the loss slot).
 void mnist_fwd_bwd(torch::Tensor X_all, torch::Tensor src_idx,
@@ -1053,12 +1172,20 @@ void mnist_fwd_bwd(torch::Tensor X_all, torch::Tensor src_idx,
                    long H, long C, double loss_scale) {
   conv_pool_fwd_idx(X_all, src_idx, idx_stride, idx_off, theta, x0,
                     pidx, cw_off, cb_off, M, F, K, IMG);
+  const bool fused = bwd_dx0_fused(theta.size(0), M, I, H, F, K, IMG,
+                                   x0.element_size());
   fc_block_launch(x0, theta, Y_all, src_idx, idx_stride, idx_off, grad,
                   dx0, dz1g, loss, w1_off, b1_off, w2_off, b2_off, M, I,
-                  H, C, loss_scale, true);
-  dw_conv_bwd_idx(dz1g, x0, dx0, pidx, X_all, src_idx, idx_stride,
-                  idx_off, grad, w1_off, b1_off, M, I, H, cw_off, cb_off,
-                  F, K, IMG);
+                  H, C, loss_scale, true, !fused);
+  if (fused) {
+    launch_dw_dx0_conv_bwd(dz1g, x0, theta, pidx, X_all, src_idx,
+                           idx_stride, idx_off, grad, w1_off, b1_off, M,
+                           I, H, cw_off, cb_off, F, K, IMG);
+  } else {
+    dw_conv_bwd_idx(dz1g, x0, dx0, pidx, X_all, src_idx, idx_stride,
+                    idx_off, grad, w1_off, b1_off, M, I, H, cw_off,
+                    cb_off, F, K, IMG);
+  }
 }
 
 #ifdef NDTA_FC_PHASE_CLOCK
@@ -1317,6 +1444,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("fc_block", &fc_block);
   mod.def("dw_conv_bwd_idx", &dw_conv_bwd_idx);
   mod.def("mnist_fwd_bwd", &mnist_fwd_bwd);
+  mod.def("dw_dx0_conv_bwd_idx", &dw_dx0_conv_bwd_idx);
+  mod.def("bwd_dx0_fused_for", &bwd_dx0_fused_for);
 #ifdef NDTA_FC_PHASE_CLOCK
   mod.def("fc_phase_clock", &fc_phase_clock);
 #endif

@@ -1031,23 +1031,24 @@ __global__ __launch_bounds__(256) void fc_fwd_split_k(
 // clamped load reads valid memory and its value is replaced by 0), so
 // the kernel is one load round trip, 16 MFMAs and a masked store, with
 // no LDS and no barrier.
+//
+// fc_dx0_tile is one wave's [16 rows from m0][16 columns from i0] tile
+// of that product (m0 < M): it leaves in g[r] the lane's masked value
+// for row m0 + acc_row(lane, r) and column i0 + (lane & 15). Rows past
+// M and columns past I hold values that mean nothing; the caller masks
+// them. fc_dx0_k stores the tile; the fused backward
+// (dw_dx0_conv_bwd_k) feeds it to the conv dW taps without a trip
+// through memory.
 template <typename T>
-__global__ __launch_bounds__(256) void fc_dx0_k(
-    const T* __restrict__ x0,     // [L*M, I]
-    const T* __restrict__ theta,  // [L, n]
-    const T* __restrict__ dz1g,   // [L*M, H]
-    T* __restrict__ dx0,          // [L*M, I]
-    long n, long w1_off, int M, int I, int H, int mask_dx0) {
+DEV_INLINE void fc_dx0_tile(
+    const T* __restrict__ x0, const T* __restrict__ theta,
+    const T* __restrict__ dz1g, long n, long w1_off, int M, int I, int H,
+    int mask_dx0, long l, int m0, int i0, int lane, T (&g)[4]) {
   using MF = gmfma::mfma_t<T>;
   using acc_t = typename MF::acc_t;
-  const long l = blockIdx.z;
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
   const int lo = lane & 15;
   const int lk = lane >> 4;
-  const int m0 = blockIdx.y * 64 + wid * 16;
-  if (m0 >= M) return;  // wave-uniform; the kernel has no barrier
-  const int i = blockIdx.x * 16 + lo;
+  const int i = i0 + lo;
   const int ic = min(i, I - 1);
   const T* W1 = theta + l * n + w1_off;
   const T* dzr = dz1g + (long)(l * (long)M + min(m0 + lo, M - 1)) * H;
@@ -1082,12 +1083,32 @@ __global__ __launch_bounds__(256) void fc_dx0_k(
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
+    // conv relu' mask: x0 IS the conv block's relu output
+    g[r] = xm[r] > T(0) ? ax0[r] + ax1[r] : T(0);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void fc_dx0_k(
+    const T* __restrict__ x0,     // [L*M, I]
+    const T* __restrict__ theta,  // [L, n]
+    const T* __restrict__ dz1g,   // [L*M, H]
+    T* __restrict__ dx0,          // [L*M, I]
+    long n, long w1_off, int M, int I, int H, int mask_dx0) {
+  using MF = gmfma::mfma_t<T>;
+  const long l = blockIdx.z;
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int m0 = blockIdx.y * 64 + wid * 16;
+  if (m0 >= M) return;  // wave-uniform; the kernel has no barrier
+  const int i = blockIdx.x * 16 + (lane & 15);
+  T g[4];
+  fc_dx0_tile<T>(x0, theta, dz1g, n, w1_off, M, I, H, mask_dx0, l, m0,
+                 blockIdx.x * 16, lane, g);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
     const int m = m0 + MF::acc_row(lane, r);
-    if (m < M && i < I) {
-      // conv relu' mask: x0 IS the conv block's relu output
-      dx0[(long)(l * (long)M + m) * I + i] =
-          xm[r] > T(0) ? ax0[r] + ax1[r] : T(0);
-    }
+    if (m < M && i < I) dx0[(long)(l * (long)M + m) * I + i] = g[r];
   }
 }
 
@@ -1138,6 +1159,154 @@ __global__ __launch_bounds__(256) void dw_conv_bwd_k(
         dY, pidx, X_all, gstack, n, cw_off, cb_off, M, F, K, IMG,
         nchunk, src_idx, idx_stride, idx_off, maxlen, bid - n_dw, tid,
         256, smem);
+  }
+}
+
+// ---------------------------------------------------------------------
+// The merged backward with dX0 folded in. fc_dx0_k existed only to
+// write dX0 to memory for the conv role above, which read each value
+// back once, as the multiplier g of one item's taps. Here the conv role
+// takes fc_dx0_k's decomposition instead: one block per (16-column
+// strip of I, 64-row group of M, node), wave w on rows [16w, 16w+16),
+// and computes the strip's dX0 tile itself (fc_dx0_tile: the same
+// operand loads and MFMA order, so every g is bit-equal to what
+// fc_dx0_k stored). A lane then holds four items (m, i), m = m0 +
+// acc_row(lane, r), i its column: it runs their K*K taps into the same
+// private acc[] as conv_pool_bwd_body and ends in the same tail.
+//
+// Requires P*P % 16 == 0 (a strip lies inside one filter, so f is
+// block-uniform, and I = F*P*P has no column tail) and K == KMAX (the
+// guard-free tap path); ext.hip bwd_dx0_fused is where that is decided.
+//
+// One load round trip brings the tile's operands, the lane's four
+// argmax bytes and its rows' source indices; the taps are the next. The
+// tap addresses do not wait for g, so the compiler issues all four
+// items' tap loads (60 at K = 5) under the tile's last MFMAs; that
+// takes about 240 VGPRs in fp64, hence the two-waves-per-SIMD bound on
+// the kernel below. NFL is how many items' taps may be in flight at
+// once: 4 wherever that fits 256 VGPRs, 1 for fp64 at K = 7 (4 spills
+// there). Rows past M are clamped for every address and carry g = 0. A wave whose rows are all past M loads nothing but
+// still runs the tail with exact-zero partials: the tail has a barrier.
+template <typename T, int KMAX>
+DEV_INLINE void dx0_conv_bwd_body(
+    const T* __restrict__ x0, const T* __restrict__ theta,
+    const T* __restrict__ dz1g, long w1_off, int H,
+    const unsigned char* __restrict__ pidx, const T* __restrict__ X_all,
+    T* __restrict__ gstack, long n, long cw_off, long cb_off, int M,
+    int I, int IMG, const long* __restrict__ src_idx, long idx_stride,
+    long idx_off, long maxlen, int sx, int gy, int l, int tid,
+    T* __restrict__ red) {
+  using MF = gmfma::mfma_t<T>;
+  constexpr int NTAP = KMAX * KMAX;
+  constexpr int NSLOT = conv::pow2_at_least(NTAP + 1);
+  constexpr int NFL = (sizeof(T) == 8 && KMAX > 5) ? 1 : 4;
+  const int P = (IMG - (KMAX - 1)) / 2;
+  const int PP = P * P;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int m0 = gy * 64 + wid * 16;
+  const int i = sx * 16 + (lane & 15);
+  const int f = (sx * 16) / PP;
+  const int pyx = i - f * PP;
+
+  T acc[NSLOT];
+#pragma unroll
+  for (int t = 0; t <= NTAP; ++t) acc[t] = T(0);
+
+  if (m0 < M) {  // wave-uniform
+    int d[4];
+    long srow[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = min(m0 + MF::acc_row(lane, r), M - 1);
+      d[r] = pidx[((long)l * M + m) * I + i];
+      srow[r] = src_idx[l * idx_stride + idx_off + m];
+    }
+    // the tap addresses hang on these eight loads alone: they stay in
+    // front of the tile's 36 (left alone the scheduler sinks them behind
+    // the first waits of the tile, a round trip of their own)
+    __builtin_amdgcn_sched_barrier(0);
+    T g[4];
+    fc_dx0_tile<T>(x0, theta, dz1g, n, w1_off, M, I, H, 1, l, m0,
+                   sx * 16, lane, g);
+    const int py2 = 2 * (pyx / P), px2 = 2 * (pyx % P);
+    const T* img[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (m0 + MF::acc_row(lane, r) >= M) g[r] = T(0);
+      const int cy = py2 + ((d[r] >> 1) & 1);
+      const int cx = px2 + (d[r] & 1);
+      img[r] = X_all + ((long)l * maxlen + srow[r]) * IMG * IMG +
+               cy * IMG + cx;
+    }
+#pragma unroll
+    for (int r0 = 0; r0 < 4; r0 += NFL) {
+      T tap[NFL][NTAP];
+#pragma unroll
+      for (int q = 0; q < NFL; ++q) {
+#pragma unroll
+        for (int ky = 0; ky < KMAX; ++ky) {
+#pragma unroll
+          for (int kx = 0; kx < KMAX; ++kx) {
+            tap[q][ky * KMAX + kx] = img[r0 + q][ky * IMG + kx];
+          }
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < NFL; ++q) {
+        acc[NTAP] += g[r0 + q];
+#pragma unroll
+        for (int t = 0; t < NTAP; ++t) acc[t] += g[r0 + q] * tap[q][t];
+      }
+      // the next group's loads stay behind this group's FMAs
+      if (r0 + NFL < 4) __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  conv::conv_bwd_reduce_tail<T, KMAX>(acc, gstack, n, cw_off, cb_off, l,
+                                      f, KMAX, tid, 256, red);
+}
+
+// Flat grid: the n_cv conv blocks first, then the dW kernel's (bx, by,
+// bz) grid; same LDS arena and block-uniform role branch as
+// dw_conv_bwd_k. The order is the reverse of dw_conv_bwd_k's, whose 768
+// conv blocks were about as short as its dW blocks. Here the 216 conv
+// blocks of the MNIST shape are the launch's critical path (two
+// dependent load round trips, 100 tap loads per thread) and the 864 dW blocks one
+// round trip each: started first, the conv blocks take a CU each and
+// the dW blocks fill in around and after them (12.6 us per call);
+// started last they wait for dW blocks to retire at two blocks per CU
+// and the launch is 16.9 us (profiles/README.md).
+template <typename T, int KMAX>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(2, 2))) void dw_dx0_conv_bwd_k(
+    // dW role (and the tile's operands: dZ = dz1, X = x0)
+    const T* __restrict__ dZ, const T* __restrict__ X,
+    long w_off, long b_off, int M, int I, int O, int dw_gx, int dw_gy,
+    // conv role
+    const T* __restrict__ theta, const unsigned char* __restrict__ pidx,
+    const T* __restrict__ X_all, long cw_off, long cb_off, int IMG,
+    int cv_gx, int cv_gy, int n_cv, const long* __restrict__ src_idx,
+    long idx_stride, long idx_off, long maxlen,
+    T* __restrict__ gstack, long n) {
+  constexpr int DW_LDS = 2 * gemm::DW_ROWS * (gemm::TILE + 1);
+  constexpr int CV_LDS = (KMAX * KMAX + 1) * 4;
+  __shared__ T smem[DW_LDS > CV_LDS ? DW_LDS : CV_LDS];
+  const int tid = threadIdx.x;
+  if ((int)blockIdx.x < n_cv) {
+    const int bid = blockIdx.x;
+    dx0_conv_bwd_body<T, KMAX>(
+        X, theta, dZ, w_off, O, pidx, X_all, gstack, n, cw_off, cb_off,
+        M, I, IMG, src_idx, idx_stride, idx_off, maxlen, bid % cv_gx,
+        (bid / cv_gx) % cv_gy, bid / (cv_gx * cv_gy), tid, smem);
+  } else {
+    const int bid = blockIdx.x - n_cv;
+    const int bx = bid % dw_gx;
+    const int by = (bid / dw_gx) % dw_gy;
+    const long bz = bid / (dw_gx * dw_gy);
+    gemm::linear_bwd_dw_body<T>(
+        dZ, X, gstack, n, w_off, b_off, M, I, O, bx, by, bz,
+        tid / gemm::TILE, tid % gemm::TILE, smem,
+        smem + gemm::DW_ROWS * (gemm::TILE + 1));
   }
 }
 

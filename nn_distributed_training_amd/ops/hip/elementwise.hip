@@ -222,6 +222,115 @@ __global__ void fused_step_k(
   }
 }
 
+// ---------------------------------------------------------------------
+// The round's dual ascent folded into its first primal step: what
+// dinno_dual_threg_k followed by fused_step_k<T, MODE, true> (nparts 1)
+// compute, bit for bit, in one launch and without the round trip of
+// duals and s through memory.
+//
+// fused_step_k updates theta in place with a thread per (node, e) and no
+// order between them, so a neighbour's theta_j[e] may already be
+// overwritten when thread (i, e) wants it. Here a BLOCK owns a strip of
+// columns for all L local nodes (blockDim = (columns, L), thread (c, l)
+// is node l of column e0 + c): every thread loads its theta into LDS,
+// one barrier, and only then does anybody store theta. Nobody else
+// touches the strip's columns, and remote rows are read-only. A
+// neighbour that is a local row is read from LDS, which a runtime row
+// number may index freely; th, the new dual and s stay in registers
+// between the two phases. The grid has as many threads as
+// fused_step_k's.
+constexpr int STEP_DUAL_THREADS = 1024;  // columns * L at the most
+constexpr int STEP_DUAL_LMAX = 16;
+
+// a * b + c with the rounding fused_step_k's two Adam moment updates
+// have as compiled: one fused multiply-add in fp64, a product and a sum
+// in fp32 (the compiler pairs the two fp32 products into one packed
+// multiply there). Bit-equality with fused_step_k needs the same here,
+// whatever the surrounding code invites the compiler to contract;
+// tests/test_step_dual_gpu.py holds the two kernels together.
+template <typename T>
+DEV_INLINE T step_mul_add(T a, T b, T c) {
+#pragma clang fp contract(off)
+  if (sizeof(T) == 8) return __builtin_fma(a, b, c);
+  return a * b + c;
+}
+
+template <typename T, int MODE, bool FIRST>
+__global__ void __launch_bounds__(STEP_DUAL_THREADS) fused_step_dual_k(
+    T* __restrict__ theta,         // [L, n] in/out (the round-start
+                                   // snapshot on entry)
+    T* __restrict__ grad,          // [L, n]
+    const T* __restrict__ remote,  // [R-L, n] received rows (may be null)
+    const int* __restrict__ offs,  // [L+1]
+    const int* __restrict__ idx,   // CSR neighbor rows
+    const int* __restrict__ deg,   // [L]
+    T* __restrict__ duals,         // [L, n] in/out
+    T* __restrict__ s_out,         // [L, n] out
+    T* __restrict__ m, T* __restrict__ v,  // Adam state (null for SGD)
+    T rho, T lr, T beta1, T beta2, T eps, T wd, T bc1, T bc2,
+    long n, int L, int zero_grad) {
+  // FIRST: the Adam moments count as zero and are not read
+  constexpr bool LOAD_MV = MODE != 2 && !FIRST;
+  __shared__ T th_s[STEP_DUAL_THREADS];  // [L][columns]
+  const int cols = blockDim.x;
+  const int c = threadIdx.x, l = threadIdx.y;
+  for (long e0 = blockIdx.x * (long)cols; e0 < n;
+       e0 += (long)gridDim.x * cols) {  // uniform over the block
+    const long e = e0 + c;
+    const bool live = e < n;
+    const long t = (long)l * n + e;
+    // all of the thread's loads go out before the barrier waits on th
+    T th = T(0), du = T(0), g = T(0), m_prev = T(0), v_prev = T(0);
+    if (live) {
+      th = theta[t];
+      du = duals[t];
+      g = grad[t];
+      if (LOAD_MV) {
+        m_prev = m[t];
+        v_prev = v[t];
+      }
+    }
+    th_s[l * cols + c] = th;
+    __syncthreads();  // the strip's theta is read; stores may follow
+    if (live) {
+      // phase 1: dinno_dual_threg_k's CSR walk, in its order
+      const int k0 = offs[l], k1 = offs[l + 1];
+      T S = T(0);
+      for (int k = k0; k < k1; ++k) {
+        const int r = idx[k];
+        S += r < L ? th_s[r * cols + c] : remote[((long)r - L) * n + e];
+      }
+      const T dg = T(k1 - k0);
+      du += rho * (dg * th - S);
+      const T sv = (dg * th + S) * T(0.5);
+      duals[t] = du;
+      s_out[t] = sv;
+      if (zero_grad) grad[t] = T(0);
+      // phase 2: fused_step_k's body (nparts 1, with penalty); an
+      // isolated node is frozen, see there
+      const int dl = deg[l];
+      if (dl != 0) {
+        g += du + T(2) * rho * (T(dl) * th - sv);
+        if (MODE == 2) {  // SGD
+          theta[t] = th - lr * g;
+        } else {
+          if (MODE == 1) {  // AdamW decoupled weight decay
+            th -= lr * wd * th;
+          } else if (wd != T(0)) {  // Adam L2
+            g += wd * th;
+          }
+          const T mt = step_mul_add(T(1) - beta1, g, beta1 * m_prev);
+          const T vt = step_mul_add(g, (T(1) - beta2) * g, beta2 * v_prev);
+          m[t] = mt;
+          v[t] = vt;
+          theta[t] = th - lr * (mt / bc1) / (::sqrt(vt / bc2) + eps);
+        }
+      }
+    }
+    __syncthreads();  // th_s is free for the next strip
+  }
+}
+
 // Graph-capture variants: the round scalars (rho, lr, per-pit Adam
 // bias corrections) live in a device buffer `sched` laid out as
 // [rho, lr, bc1_pit0, bc2_pit0, bc1_pit1, ...] and batch offsets in an

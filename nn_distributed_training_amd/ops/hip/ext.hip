@@ -1188,6 +1188,104 @@ void mnist_fwd_bwd(torch::Tensor X_all, torch::Tensor src_idx,
   }
 }
 
+// Whether the first primal step of a DiNNO round carries the round's
+// dual ascent (elementwise.hip fused_step_dual_k) instead of following a
+// dinno_dual_threg launch. This is the only place the condition is
+// written: a plain [L, n] gradient (nparts 1; the megakernel's per-tile
+// slabs keep the two launches) and at most STEP_DUAL_LMAX local nodes,
+// which one block's threads cover. NDTA_STEP_DUAL=0 keeps the two
+// launches for A/B runs.
+inline bool step_dual_fused(long L, long nparts) {
+  static const bool off = []() {
+    const char* e = getenv("NDTA_STEP_DUAL");
+    return e && e[0] == '0';
+  }();
+  return !off && nparts == 1 && L >= 1 && L <= ew::STEP_DUAL_LMAX;
+}
+
+bool step_dual_fused_for(long L, long nparts) {
+  return step_dual_fused(L, nparts);
+}
+
+// columns per block of fused_step_dual_k (the block is columns x L
+// threads): 64, so the MNIST model's n = 28,440 at L = 8 is 445 blocks of
+// 512 threads, fused_step_k's thread count; 32 and 128 measured the same
+// within the run-to-run spread (profiles/README.md).
+constexpr int STEP_DUAL_COLS = 64;
+static_assert(STEP_DUAL_COLS * ew::STEP_DUAL_LMAX <= ew::STEP_DUAL_THREADS,
+              "a block of columns x L threads must fit");
+
+// Dual ascent + first primal step of a DiNNO round: the results of
+// dinno_dual_threg followed by fused_step (with penalty), bit for bit.
+// One launch where step_dual_fused says so, else those two.
+void fused_step_dual(torch::Tensor theta, torch::Tensor grad,
+                     c10::optional<torch::Tensor> remote,
+                     torch::Tensor offs, torch::Tensor idx,
+                     torch::Tensor deg, torch::Tensor duals,
+                     torch::Tensor s_out,
+                     c10::optional<torch::Tensor> m,
+                     c10::optional<torch::Tensor> v,
+                     double rho, double lr, double beta1, double beta2,
+                     double eps, double wd, long step_t, long mode,
+                     bool first_step, long nparts, bool zero_grad) {
+  CHECK_DEV(theta); CHECK_DEV(grad); CHECK_DEV(duals); CHECK_DEV(s_out);
+  const long L = theta.size(0), n = theta.size(1);
+  if (!step_dual_fused(L, nparts)) {
+    dinno_dual_threg(theta, remote, offs, idx, duals, s_out, rho);
+    fused_step(theta, grad, duals, s_out, deg, m, v, rho, lr, beta1,
+               beta2, eps, wd, step_t, mode, first_step, nparts,
+               zero_grad);
+    return;
+  }
+  TORCH_CHECK(grad.numel() == L * n && duals.numel() == L * n &&
+                  s_out.numel() == L * n,
+              "fused_step_dual: grad, duals and s must be [L, n]");
+  CHECK_DEV(offs); CHECK_DEV(idx); CHECK_DEV(deg);
+  TORCH_CHECK(offs.scalar_type() == torch::kInt &&
+                  idx.scalar_type() == torch::kInt &&
+                  deg.scalar_type() == torch::kInt &&
+                  offs.numel() == L + 1 && deg.numel() == L,
+              "fused_step_dual: int32 offs [L+1], idx and deg [L] expected");
+  for (const auto* t : {&remote, &m, &v}) {
+    TORCH_CHECK(!t->has_value() ||
+                    ((*t)->is_cuda() && (*t)->is_contiguous() &&
+                     (*t)->scalar_type() == theta.scalar_type()),
+                "fused_step_dual: remote, m and v must be contiguous on "
+                "GPU, of theta's dtype");
+  }
+  TORCH_CHECK(grad.scalar_type() == theta.scalar_type() &&
+                  duals.scalar_type() == theta.scalar_type() &&
+                  s_out.scalar_type() == theta.scalar_type() &&
+                  (!remote.has_value() || remote->numel() % n == 0),
+              "fused_step_dual: grad, duals, s of theta's dtype; remote "
+              "[R-L, n]");
+  TORCH_CHECK(mode == 2 || (m.has_value() && v.has_value() &&
+                            m->numel() == L * n && v->numel() == L * n),
+              "fused_step_dual: Adam modes need m and v [L, n]");
+  const int cols = STEP_DUAL_COLS;
+  DISPATCH_FT(theta, {
+    const scalar_t bc1 =
+        (scalar_t)(1.0 - std::pow(beta1, (double)step_t));
+    const scalar_t bc2 =
+        (scalar_t)(1.0 - std::pow(beta2, (double)step_t));
+    dispatch_mode_pen(mode, first_step, [&](auto mode_c, auto first_c) {
+      hipLaunchKernelGGL(
+          (ew::fused_step_dual_k<scalar_t, decltype(mode_c)::value,
+                                 decltype(first_c)::value>),
+          dim3(grid_1d(n, cols)), dim3(cols, L), 0, cur_stream(),
+          theta.data_ptr<scalar_t>(), grad.data_ptr<scalar_t>(),
+          opt_ptr<scalar_t>(remote), offs.data_ptr<int>(),
+          idx.data_ptr<int>(), deg.data_ptr<int>(),
+          duals.data_ptr<scalar_t>(), s_out.data_ptr<scalar_t>(),
+          opt_ptr<scalar_t>(m), opt_ptr<scalar_t>(v),
+          (scalar_t)rho, (scalar_t)lr, (scalar_t)beta1,
+          (scalar_t)beta2, (scalar_t)eps, (scalar_t)wd, bc1, bc2,
+          n, (int)L, zero_grad ? 1 : 0);
+    });
+  });
+  HIP_CHECK_LAST();
+}
+
 #ifdef NDTA_FC_PHASE_CLOCK
 // diagnostic build only: [blocks, 8] wall_clock64 stamps of the last
 // fc_block launch (see fused_mnist.hip FC_STAMP)
@@ -1446,6 +1544,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("mnist_fwd_bwd", &mnist_fwd_bwd);
   mod.def("dw_dx0_conv_bwd_idx", &dw_dx0_conv_bwd_idx);
   mod.def("bwd_dx0_fused_for", &bwd_dx0_fused_for);
+  mod.def("step_dual_fused_for", &step_dual_fused_for);
+  mod.def("fused_step_dual", &fused_step_dual);
 #ifdef NDTA_FC_PHASE_CLOCK
   mod.def("fc_phase_clock", &fc_phase_clock);
 #endif

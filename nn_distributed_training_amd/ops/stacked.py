@@ -1185,11 +1185,6 @@ class DiNNOStackedDriver:
                     pr.layout, list(pr.graph.edges()), [eng.theta],
                     [dests],
                 )
-        with _timer("dual_threg"):
-            ext.dinno_dual_threg(
-                eng.theta, rbuf, offs, idx, self.duals, self.s, self.rho
-            )
-
         if not self.persistent:
             # the kernel's first_step flag zeroes the moments logically
             self.step_t = 0
@@ -1197,6 +1192,20 @@ class DiNNOStackedDriver:
             opt.primal_lr[0] if self.persistent else opt.primal_lr[k]
         )
 
+        # The round's dual ascent rides in its first primal step
+        # (ext.hip fused_step_dual: one launch where step_dual_fused
+        # says so, else dinno_dual_threg + fused_step from that call):
+        # nothing before that step reads duals or s, and everything
+        # before it (the exchange above, the first forward/backward)
+        # reads the round-start theta, which only the step changes.
+        mv = (
+            None if self.mode == 2 else self.m,
+            None if self.mode == 2 else self.v,
+        )
+        if self.pits == 0:  # no step to carry it
+            ext.dinno_dual_threg(
+                eng.theta, rbuf, offs, idx, self.duals, self.s, self.rho
+            )
         want_tl = bool(getattr(pr, "track_tloss", False))
         for pi in range(self.pits):
             wl = want_tl and pi == self.pits - 1
@@ -1206,14 +1215,20 @@ class DiNNOStackedDriver:
             with _timer("fused_step"):
                 self.step_t += 1
                 zg = nparts == 1 and grad_t is eng.grad
-                ext.fused_step(
-                    eng.theta, grad_t, self.duals, self.s, deg,
-                    None if self.mode == 2 else self.m,
-                    None if self.mode == 2 else self.v,
-                    self.rho, lr, 0.9, 0.999, 1e-8, self.wd,
-                    self.step_t, self.mode, self.step_t == 1, nparts,
-                    zg,
+                adam = (
+                    self.rho, lr, 0.9, 0.999, 1e-8, self.wd, self.step_t,
+                    self.mode, self.step_t == 1,
                 )
+                if pi == 0:
+                    ext.fused_step_dual(
+                        eng.theta, grad_t, rbuf, offs, idx, deg,
+                        self.duals, self.s, *mv, *adam, nparts, zg,
+                    )
+                else:
+                    ext.fused_step(
+                        eng.theta, grad_t, self.duals, self.s, deg,
+                        *mv, *adam, nparts, zg,
+                    )
                 if zg:
                     eng.grad_is_zero = True
 

@@ -9,6 +9,7 @@
 #include "gemm_mfma.hip"
 #include "conv.hip"
 #include "losses.hip"
+#include "rollout.hip"
 #include "fused_mnist.hip"
 
 #include <ATen/hip/HIPContext.h>
@@ -847,6 +848,131 @@ void ppo_loss_bwd(torch::Tensor mean, torch::Tensor acts,
   HIP_CHECK_LAST();
 }
 
+// One batch of SimpleTagEnv episodes on the device (rollout.hip
+// ppo_rollout_k), one block per episode; the layer lists are the
+// actor's shifted_plan (act: 0 none, 1 relu) and envp the env's
+// constants in EnvParams order. Weights go to LDS where all N actors
+// fit beside the reward row, else they are read in place;
+// NDTA_ROLLOUT_WLDS=0/1 forces one or the other for A/B runs (1 only
+// where they fit).
+void ppo_rollout(torch::Tensor theta, std::vector<long> in_dims,
+                 std::vector<long> out_dims, std::vector<long> w_offs,
+                 std::vector<long> b_offs, std::vector<long> act_ids,
+                 torch::Tensor resets, torch::Tensor obst,
+                 torch::Tensor eps, torch::Tensor obs,
+                 torch::Tensor acts, torch::Tensor logp,
+                 torch::Tensor rews, torch::Tensor rtgs,
+                 torch::Tensor ep_rew, long M, long ep_len, double cov,
+                 double gamma, std::vector<double> envp) {
+  CHECK_DEV(theta); CHECK_DEV(resets); CHECK_DEV(obst); CHECK_DEV(eps);
+  CHECK_DEV(obs); CHECK_DEV(acts); CHECK_DEV(logp); CHECK_DEV(rews);
+  CHECK_DEV(rtgs); CHECK_DEV(ep_rew);
+  TORCH_CHECK(theta.dim() == 2, "theta must be the [N, n] stack");
+  const long N = theta.size(0), n = theta.size(1);
+  const long A = rollout::ACT_DIM;
+  const long nl = (long)in_dims.size();
+  TORCH_CHECK(N >= 1 && N <= rollout::MAX_N,
+              "ppo_rollout supports at most ", rollout::MAX_N, " nodes");
+  TORCH_CHECK(nl >= 1 && nl <= rollout::MAX_LAYERS,
+              "ppo_rollout supports at most ", rollout::MAX_LAYERS,
+              " layers");
+  TORCH_CHECK((long)out_dims.size() == nl && (long)w_offs.size() == nl &&
+                  (long)b_offs.size() == nl && (long)act_ids.size() == nl,
+              "layer lists differ in length");
+  TORCH_CHECK(envp.size() == 11, "envp must hold EnvParams' 11 values");
+  TORCH_CHECK(M >= 1 && ep_len >= 1 && ep_len <= 4096 &&
+                  N * M < (1L << 27),
+              "ppo_rollout: bad M / ep_len");
+  TORCH_CHECK(cov > 0, "cov must be positive");
+  const long obs_dim = 2 * N + 6;
+  const long E = (M + ep_len - 1) / ep_len;
+  rollout::Plan plan;
+  plan.nl = (int)nl;
+  long span = 0, W = obs_dim;
+  for (long i = 0; i < nl; ++i) {
+    const long I = in_dims[i], O = out_dims[i];
+    TORCH_CHECK(I >= 1 && I <= rollout::MAX_W && O >= 1 &&
+                    O <= rollout::MAX_W,
+                "ppo_rollout supports layer widths <= ", rollout::MAX_W);
+    TORCH_CHECK(I == (i == 0 ? obs_dim : out_dims[i - 1]),
+                "layer ", i, " does not take the layer below's output");
+    TORCH_CHECK(act_ids[i] == ACT_NONE || act_ids[i] == ACT_RELU,
+                "ppo_rollout supports relu/none activations");
+    TORCH_CHECK(w_offs[i] >= 0 && b_offs[i] >= 0 &&
+                    w_offs[i] + I * O <= n && b_offs[i] + O <= n,
+                "layer ", i, " lies outside the parameter row");
+    plan.in_dim[i] = (int)I; plan.out_dim[i] = (int)O;
+    plan.w_off[i] = (int)w_offs[i]; plan.b_off[i] = (int)b_offs[i];
+    plan.relu[i] = act_ids[i] == ACT_RELU ? 1 : 0;
+    span = std::max(span, std::max(w_offs[i] + I * O, b_offs[i] + O));
+    W = std::max(W, O);
+  }
+  TORCH_CHECK(out_dims[nl - 1] == A, "the actor's head must be ", A,
+              " wide");
+  TORCH_CHECK(n < (1L << 31), "parameter row too long");
+  TORCH_CHECK(resets.scalar_type() == torch::kDouble &&
+                  resets.numel() == E * (N + 1) * 2,
+              "resets must be [E, N+1, 2] double");
+  const long n_obst = obst.numel() / 2;
+  TORCH_CHECK(obst.scalar_type() == torch::kDouble &&
+                  obst.numel() == 2 * n_obst &&
+                  n_obst <= rollout::MAX_OBST,
+              "obst must be [<= ", rollout::MAX_OBST, ", 2] double");
+  TORCH_CHECK(eps.numel() == E * ep_len * N * A,
+              "eps must be [E, ep_len, N, A]");
+  TORCH_CHECK(obs.numel() == N * M * obs_dim && acts.numel() == N * M * A &&
+                  logp.numel() == N * M && rtgs.numel() == N * M,
+              "obs/acts/logp/rtgs must be [N*M, .]");
+  TORCH_CHECK(rews.scalar_type() == torch::kDouble && rews.numel() == M &&
+                  ep_rew.scalar_type() == torch::kDouble &&
+                  ep_rew.numel() == E,
+              "rews [M] and ep_rew [E] must be double");
+  for (const torch::Tensor* t : {&eps, &obs, &acts, &logp, &rtgs}) {
+    TORCH_CHECK(t->scalar_type() == theta.scalar_type(),
+                "ppo_rollout tensors must share theta's dtype");
+  }
+  rollout::EnvParams env{envp[0], envp[1], envp[2], envp[3], envp[4],
+                         envp[5], envp[6], envp[7], envp[8], envp[9],
+                         envp[10]};
+  // a thread per (node, unit) and per observation element, plus the
+  // reward thread at the block's end
+  const long threads =
+      (std::max(N * W, N * obs_dim + 1) + 63) / 64 * 64;
+  TORCH_CHECK(threads <= 1024, "ppo_rollout block too large");
+  static const int force_wlds = []() {
+    const char* e = getenv("NDTA_ROLLOUT_WLDS");
+    return e ? (e[0] == '0' ? 0 : 1) : -1;
+  }();
+  const double logc =
+      0.5 * (double)A * std::log(2.0 * 3.14159265358979323846 * cov);
+  DISPATCH_FT(theta, {
+    const size_t rew_bytes = (size_t)ep_len * sizeof(double);
+    const size_t w_bytes = (size_t)(N * span) * sizeof(scalar_t);
+    // static LDS of the kernel: the two activation buffers + env state
+    const size_t fixed =
+        2 * rollout::MAX_N * rollout::MAX_W * sizeof(scalar_t) + 1024;
+    const bool fits = fixed + rew_bytes + w_bytes <= 156 * 1024;
+    const bool wlds = fits && force_wlds != 0;
+    auto launch = [&](auto wlds_c) {
+      hipLaunchKernelGGL(
+          (rollout::ppo_rollout_k<scalar_t, decltype(wlds_c)::value>),
+          dim3(E), dim3(threads),
+          rew_bytes + (decltype(wlds_c)::value ? w_bytes : 0),
+          cur_stream(), theta.data_ptr<scalar_t>(), n, plan, (int)span,
+          (int)W, resets.data_ptr<double>(), obst.data_ptr<double>(),
+          eps.data_ptr<scalar_t>(), obs.data_ptr<scalar_t>(),
+          acts.data_ptr<scalar_t>(), logp.data_ptr<scalar_t>(),
+          rews.data_ptr<double>(), rtgs.data_ptr<scalar_t>(),
+          ep_rew.data_ptr<double>(), (int)N, (int)n_obst, (int)M,
+          (int)ep_len, (scalar_t)std::sqrt(cov), (scalar_t)logc, gamma,
+          env);
+    };
+    if (wlds) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
+  HIP_CHECK_LAST();
+}
+
 // fc1 dW/db + gather-sourced conv dW/db in ONE launch (fused_mnist.hip
 // dw_conv_bwd_k) where the dW shape takes the small store-path kernel;
 // any other shape keeps the two launches. Same preconditions as
@@ -1537,6 +1663,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("bce_bwd", &bce_bwd);
   mod.def("regression_bwd", &regression_bwd);
   mod.def("ppo_loss_bwd", &ppo_loss_bwd);
+  mod.def("ppo_rollout", &ppo_rollout);
   mod.def("feistel_perm", &feistel_perm);
   mod.def("consensus_cdist", &consensus_cdist);
   mod.def("fc_block", &fc_block);

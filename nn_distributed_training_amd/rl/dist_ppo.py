@@ -8,6 +8,11 @@ Gaussian action sampling with a fixed covariance (cov 0.5, reference
 dist_ppo.py:325-351). Hyperparameters come from a plain config dict (the
 reference's ``exec``-based injection, dist_ppo.py:426-427, is not
 reproduced).
+
+``rollout_engine: "device"`` (default ``"host"``) collects the batch and
+runs ``evaluate`` in one kernel launch instead (rl/device_rollout.py);
+its action noise comes from another random stream than
+``MultivariateNormal.sample``'s.
 """
 
 from __future__ import annotations
@@ -69,6 +74,41 @@ class DistPPOProblem:
         self.value_engine = None
         self.total_timesteps = 0
         self.ep_rew_history = []  # mean episodic reward per batch
+        # rollout_engine "device": the DeviceRollout, and the [N*M, .]
+        # tensors of its last batch (self.buf then holds views of them)
+        self.rollout_engine = self.conf.get("rollout_engine", "host")
+        self.device_rollout = self._resolve_rollout_engine()
+        self.device_buf = None
+
+    # ------------------------------------------------------------------
+    def _resolve_rollout_engine(self):
+        """The DeviceRollout for ``rollout_engine: "device"``, None for
+        ``"host"``. A device request that cannot be served is an error,
+        never a quiet host rollout."""
+        if self.rollout_engine == "host":
+            return None
+        if self.rollout_engine != "device":
+            raise ValueError(
+                f"rollout_engine must be 'host' or 'device', got "
+                f"{self.rollout_engine!r}"
+            )
+        if self.device.type != "cuda":
+            raise ValueError(
+                "rollout_engine='device' needs a GPU problem; this one "
+                f"is on {self.device}"
+            )
+        from ..ops import get_ext
+
+        try:
+            get_ext()
+        except Exception as e:  # noqa: BLE001
+            raise ValueError(
+                "rollout_engine='device' needs the HIP extension, which "
+                f"failed to load: {e}"
+            ) from e
+        from .device_rollout import DeviceRollout
+
+        return DeviceRollout(self)
 
     # ------------------------------------------------------------------
     def node_vector(self, i) -> torch.Tensor:
@@ -112,6 +152,8 @@ class DistPPOProblem:
         serial env stepping, per-predator trajectories, rewards-to-go,
         advantage = rtg - V(obs) normalized per node.
         """
+        if self.device_rollout is not None:
+            return self._rollout_device()
         conf = self.conf
         T = conf["timesteps_per_batch"]
         obs_buf = [[] for _ in range(self.N)]
@@ -198,6 +240,49 @@ class DistPPOProblem:
                 self.buf[i]["adv"] = adv[i]
 
     # ------------------------------------------------------------------
+    def _theta_stack(self):
+        return torch.stack(
+            [self.node_vector(i).detach() for i in range(self.N)]
+        ).contiguous()
+
+    def _rollout_device(self):
+        """The same batch from one ``ext.ppo_rollout`` launch
+        (rl/device_rollout.py): ``self.buf[i]`` are views of the
+        ``[N*M, .]`` tensors kept in ``self.device_buf``."""
+        N = self.N
+        theta = self._theta_stack()
+        out = self.device_rollout.run(theta)
+        M = out["M"]
+        self.total_timesteps += M
+        self.ep_rew_history.append(float(out["ep_rew"].mean()))
+
+        rtgs = out["rtgs"].view(N, M)
+        if self.value_engine is None:
+            with torch.no_grad():
+                v = torch.stack([
+                    self.critics[i](out["obs"][i * M:(i + 1) * M])
+                    .squeeze(-1)
+                    for i in range(N)
+                ])
+        else:
+            eng = self.value_engine
+            eng.load_device_rollout(out)
+            v = eng.values(theta)
+        adv = rtgs - v
+        adv = (adv - adv.mean(dim=1, keepdim=True)) / (
+            adv.std(dim=1, keepdim=True) + 1e-10
+        )
+        out["adv"] = adv.reshape(-1)
+        self.device_buf = out
+        self.buf = {
+            i: {
+                k: out[k][i * M:(i + 1) * M]
+                for k in ("obs", "acts", "logp", "rtgs", "adv")
+            }
+            for i in range(N)
+        }
+
+    # ------------------------------------------------------------------
     def local_batch_loss(self, i):
         """Clipped PPO surrogate + critic MSE on node i's rollout
         (reference ev_ppo_loss, dist_ppo.py:128-156)."""
@@ -244,6 +329,18 @@ class DistPPOProblem:
     # ------------------------------------------------------------------
     def evaluate(self, episodes=3):
         """Mean episodic reward with deterministic (mean) actions."""
+        if self.device_rollout is not None:
+            # the rollout kernel with zero noise: act = mean
+            dr = self.device_rollout
+            _, ep_len, _ = dr.shape()
+            eps = torch.zeros(
+                episodes, ep_len, self.N, self.env.act_dim,
+                device=self.device, dtype=dr.dtype,
+            )
+            out = dr.run(
+                self._theta_stack(), eps=eps, M=episodes * ep_len
+            )
+            return float(out["ep_rew"].mean())
         totals = []
         for _ in range(episodes):
             obs = self.env.reset()

@@ -84,8 +84,14 @@ class _PPOBase:
         return engine
 
     def _begin_round(self):
-        """Hand the round's rollout to the stacked engine."""
-        if self.engine is not None:
+        """Hand the round's rollout to the stacked engine: a device
+        rollout's [N*M, .] tensors as they are, a host rollout's
+        per-node buffers concatenated."""
+        if self.engine is None:
+            return
+        if self.pr.device_buf is not None:
+            self.engine.load_device_rollout(self.pr.device_buf)
+        else:
             self.engine.load_rollout(self.pr.buf)
 
     def _theta_stack(self):
@@ -267,8 +273,10 @@ class DiNNOPPO(_PPOBase):
         next autograd sees it. With ``"stacked"`` it is
         ``StackedPPOEngine.grads``: theta stays on the device for all
         primal iterations (grads, fused_step, nothing in between) and
-        reaches the modules once, at the end of the round. Rollouts are
-        host-side env stepping with either engine."""
+        reaches the modules once, at the end of the round. The rollout is
+        the problem's: host-side env stepping, or with ``rollout_engine:
+        "device"`` one kernel launch whose tensors the stacked engine
+        adopts without a copy (``_begin_round``)."""
         from ..ops import get_ext
 
         ext = get_ext()

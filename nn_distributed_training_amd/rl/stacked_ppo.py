@@ -175,6 +175,24 @@ class StackedPPOEngine:
         self.rtgs = cat("rtgs")
         self.adv = cat("adv")
 
+    def load_device_rollout(self, ro):
+        """Adopt the ``[N*M, .]`` tensors of ``DeviceRollout.run`` as
+        they are (no copies; ``ro["adv"]`` once the problem has filled
+        it in - :meth:`values` needs the observations only)."""
+        M = int(ro["M"])
+        for key in ("obs", "acts", "logp", "rtgs"):
+            t = ro[key]
+            assert t.shape[0] == self.N * M and t.is_contiguous()
+            assert t.dtype == self.dtype and t.is_cuda
+        self.obs = ro["obs"]
+        self.acts = ro["acts"]
+        self.old_logp = ro["logp"]
+        self.rtgs = ro["rtgs"]
+        if "adv" in ro:
+            self.adv = ro["adv"].contiguous()
+        if M != self.M:
+            self._alloc(M)
+
     def load_obs(self, obs_list):
         """Stack per-node observations only (enough for :meth:`values`)."""
         M = int(obs_list[0].shape[0])

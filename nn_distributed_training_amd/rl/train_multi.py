@@ -59,12 +59,19 @@ def main(argv=None):
         help="PPO gradients by per-node autograd (torch) or batched "
              "over all nodes on the HIP kernels (stacked; needs a GPU)",
     )
+    p.add_argument(
+        "--rollout-engine", default="host", choices=["host", "device"],
+        help="rollouts by stepping the numpy env on the host (host) or "
+             "a whole batch of episodes in one HIP kernel launch "
+             "(device; needs a GPU; other action-noise stream than host)",
+    )
     args = p.parse_args(argv)
 
     torch.manual_seed(args.seed)
     conf = default_conf(args.alg)
     conf["output_dir"] = args.out
     conf["grad_engine"] = args.grad_engine
+    conf["rollout_engine"] = args.rollout_engine
     if args.max_timesteps:
         conf["max_rl_timesteps"] = args.max_timesteps
 

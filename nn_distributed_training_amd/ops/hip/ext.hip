@@ -10,6 +10,7 @@
 #include "conv.hip"
 #include "losses.hip"
 #include "rollout.hip"
+#include "advantage.hip"
 #include "fused_mnist.hip"
 
 #include <ATen/hip/HIPContext.h>
@@ -973,6 +974,68 @@ void ppo_rollout(torch::Tensor theta, std::vector<long> in_dims,
   HIP_CHECK_LAST();
 }
 
+// GAE(lambda) advantages of all nodes in one launch (advantage.hip
+// ppo_gae_k, one block per node): v [L*M] of T, rews double, [M] with
+// rew_stride 0 (the device rollout's shared reward row) or [L*M] with
+// rew_stride M; adv and the optional ret (the lambda-returns) [L*M] of
+// T. Uniform episodes of ep_len steps, the last one cut at M. The
+// unnormalised advantages wait in LDS for the node's mean and std; above
+// LDS_MAX_M steps they wait in global memory instead: in adv itself
+// where T is double, else in a double row allocated here.
+void ppo_gae(torch::Tensor v, torch::Tensor rews, long rew_stride,
+             torch::Tensor adv, c10::optional<torch::Tensor> ret, long M,
+             long ep_len, double gamma, double lam) {
+  CHECK_DEV(v); CHECK_DEV(rews); CHECK_DEV(adv);
+  TORCH_CHECK(M >= 2, "ppo_gae: M must be at least 2 (unbiased std)");
+  TORCH_CHECK(M < (1L << 31) - advantage::BLOCK, "ppo_gae: M too large");
+  TORCH_CHECK(ep_len >= 1 && ep_len <= 4096,
+              "ppo_gae: ep_len must be in 1..4096");
+  TORCH_CHECK(gamma >= 0.0 && gamma <= 1.0 && lam >= 0.0 && lam <= 1.0,
+              "ppo_gae: gamma and lam must be in [0, 1]");
+  TORCH_CHECK(v.numel() >= M && v.numel() % M == 0,
+              "ppo_gae: v must be [L*M]");
+  const long L = v.numel() / M;
+  TORCH_CHECK(L < (1L << 31), "ppo_gae: too many nodes for one grid");
+  TORCH_CHECK(v.scalar_type() == torch::kFloat ||
+                  v.scalar_type() == torch::kDouble,
+              "ppo_gae: v must be float or double");
+  TORCH_CHECK(rews.scalar_type() == torch::kDouble,
+              "ppo_gae: rews must be double");
+  TORCH_CHECK((rew_stride == 0 && rews.numel() == M) ||
+                  (rew_stride == M && rews.numel() == L * M),
+              "ppo_gae: rews must be [M] with stride 0 or [L*M] with "
+              "stride M");
+  TORCH_CHECK(adv.numel() == L * M &&
+                  adv.scalar_type() == v.scalar_type() &&
+                  adv.data_ptr() != v.data_ptr(),
+              "ppo_gae: adv must be [L*M] of v's dtype, not v itself");
+  if (ret.has_value()) {
+    CHECK_DEV(*ret);
+    TORCH_CHECK(ret->numel() == L * M &&
+                    ret->scalar_type() == v.scalar_type() &&
+                    ret->data_ptr() != v.data_ptr() &&
+                    ret->data_ptr() != adv.data_ptr(),
+                "ppo_gae: ret must be [L*M] of v's dtype, apart from v "
+                "and adv");
+  }
+  const bool lds = M <= advantage::LDS_MAX_M;
+  torch::Tensor work;
+  if (!lds) {
+    work = v.scalar_type() == torch::kDouble
+               ? adv
+               : torch::empty({L * M}, v.options().dtype(torch::kDouble));
+  }
+  DISPATCH_FT(v, {
+    hipLaunchKernelGGL(advantage::ppo_gae_k<scalar_t>, dim3(L),
+        dim3(advantage::BLOCK), lds ? (size_t)M * sizeof(double) : 0,
+        cur_stream(), v.data_ptr<scalar_t>(), rews.data_ptr<double>(),
+        rew_stride, adv.data_ptr<scalar_t>(), opt_ptr<scalar_t>(ret),
+        lds ? nullptr : work.data_ptr<double>(), (int)M, (int)ep_len,
+        gamma, gamma * lam);
+  });
+  HIP_CHECK_LAST();
+}
+
 // fc1 dW/db + gather-sourced conv dW/db in ONE launch (fused_mnist.hip
 // dw_conv_bwd_k) where the dW shape takes the small store-path kernel;
 // any other shape keeps the two launches. Same preconditions as
@@ -1664,6 +1727,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("regression_bwd", &regression_bwd);
   mod.def("ppo_loss_bwd", &ppo_loss_bwd);
   mod.def("ppo_rollout", &ppo_rollout);
+  mod.def("ppo_gae", &ppo_gae);
   mod.def("feistel_perm", &feistel_perm);
   mod.def("consensus_cdist", &consensus_cdist);
   mod.def("fc_block", &fc_block);

@@ -13,6 +13,11 @@ reproduced).
 runs ``evaluate`` in one kernel launch instead (rl/device_rollout.py);
 its action noise comes from another random stream than
 ``MultivariateNormal.sample``'s.
+
+``gae_lambda`` (default ``None``: the reference's Monte-Carlo estimator
+above) switches the advantages to GAE(lambda) (rl/advantages.py), and
+``critic_target: "lambda"`` (default ``"rtg"``) then regresses the critic
+on the lambda-returns instead of the rewards-to-go.
 """
 
 from __future__ import annotations
@@ -79,6 +84,53 @@ class DistPPOProblem:
         self.rollout_engine = self.conf.get("rollout_engine", "host")
         self.device_rollout = self._resolve_rollout_engine()
         self.device_buf = None
+        self.gae_lambda, self.critic_target = self._resolve_estimator()
+
+    # ------------------------------------------------------------------
+    def _resolve_estimator(self):
+        """``(gae_lambda, critic_target)`` of the config, checked."""
+        lam = self.conf.get("gae_lambda")
+        target = self.conf.get("critic_target", "rtg")
+        if lam is not None:
+            lam = float(lam)
+            if not 0.0 <= lam <= 1.0:
+                raise ValueError(
+                    f"gae_lambda must be in [0, 1] or None, got {lam}"
+                )
+        if target not in ("rtg", "lambda"):
+            raise ValueError(
+                f"critic_target must be 'rtg' or 'lambda', got {target!r}"
+            )
+        if target == "lambda" and lam is None:
+            raise ValueError(
+                "critic_target='lambda' needs a gae_lambda: the "
+                "lambda-returns come from the GAE estimator"
+            )
+        return lam, target
+
+    def _gae(self, v, rews, ep_lens):
+        """GAE(lambda) from the critic values ``v [N, M]`` and the
+        rewards (``[M]`` shared or ``[N, M]``, double): the normalised
+        advantages and the critic target (None under ``"rtg"``), both
+        ``[N, M]`` of ``v``'s dtype. One ``ppo_gae`` launch where the
+        extension is guaranteed (device rollout or stacked engine) and
+        the episodes are uniform, the torch mirror otherwise."""
+        from . import advantages as gae
+
+        gamma, lam = float(self.conf["gamma"]), self.gae_lambda
+        want_ret = self.critic_target == "lambda"
+        ep_len = gae.uniform_ep_len(ep_lens)
+        have_ext = (
+            self.device_rollout is not None
+            or self.value_engine is not None
+        )
+        if have_ext and ep_len is not None:
+            return gae.gae_advantages_hip(
+                v, rews, ep_len, gamma, lam, want_ret
+            )
+        A, ret = gae.gae_advantages_torch(v, rews, ep_lens, gamma, lam)
+        adv = gae.normalize_advantages(A).to(v.dtype)
+        return adv, ret.to(v.dtype) if want_ret else None
 
     # ------------------------------------------------------------------
     def _resolve_rollout_engine(self):
@@ -150,7 +202,11 @@ class DistPPOProblem:
 
         Parity with reference split_rollout_marl (dist_ppo.py:171-293):
         serial env stepping, per-predator trajectories, rewards-to-go,
-        advantage = rtg - V(obs) normalized per node.
+        advantage = rtg - V(obs) normalized per node. ``buf[i]["rews"]``
+        keeps the per-step rewards (double). With ``gae_lambda`` the
+        advantages are GAE(lambda) instead (``_finish_gae``), and
+        ``critic_target: "lambda"`` adds the lambda-returns as
+        ``buf[i]["vtarg"]``.
         """
         if self.device_rollout is not None:
             return self._rollout_device()
@@ -215,16 +271,25 @@ class DistPPOProblem:
                 rtgs, dtype=torch.get_default_dtype(),
                 device=self.device,
             )
+            rews_i = torch.as_tensor(
+                [r for ep in rews_eps[i] for r in ep],
+                dtype=torch.float64, device=self.device,
+            )
             self.buf[i] = dict(
                 obs=obs_i, acts=acts_i, logp=logp_i, rtgs=rtgs_i,
+                rews=rews_i,
             )
+            if self.gae_lambda is not None:
+                continue
             if self.value_engine is None:
                 with torch.no_grad():
                     v = self.critics[i](obs_i).squeeze(-1)
                 adv = rtgs_i - v
                 adv = (adv - adv.mean()) / (adv.std() + 1e-10)
                 self.buf[i]["adv"] = adv
-        if self.value_engine is not None:
+        if self.gae_lambda is not None:
+            self._finish_gae([len(ep) for ep in rews_eps[0]])
+        elif self.value_engine is not None:
             # V(obs) of all nodes from the stacked critic forward, then
             # the same per-node normalization batched over [N, M]
             eng = self.value_engine
@@ -238,6 +303,28 @@ class DistPPOProblem:
             )
             for i in range(self.N):
                 self.buf[i]["adv"] = adv[i]
+
+    def _finish_gae(self, ep_lens):
+        """``adv`` (and ``vtarg``) of a host rollout's buffers under
+        ``gae_lambda``: V(obs) from the stacked engine where one is
+        attached, else from the critic modules."""
+        N = self.N
+        if self.value_engine is None:
+            with torch.no_grad():
+                v = torch.stack([
+                    self.critics[i](self.buf[i]["obs"]).squeeze(-1)
+                    for i in range(N)
+                ])
+        else:
+            eng = self.value_engine
+            eng.load_obs([self.buf[i]["obs"] for i in range(N)])
+            v = eng.values(eng.stack_from_modules())
+        rews = torch.stack([self.buf[i]["rews"] for i in range(N)])
+        adv, vtarg = self._gae(v, rews, ep_lens)
+        for i in range(N):
+            self.buf[i]["adv"] = adv[i]
+            if vtarg is not None:
+                self.buf[i]["vtarg"] = vtarg[i]
 
     # ------------------------------------------------------------------
     def _theta_stack(self):
@@ -268,19 +355,29 @@ class DistPPOProblem:
             eng = self.value_engine
             eng.load_device_rollout(out)
             v = eng.values(theta)
-        adv = rtgs - v
-        adv = (adv - adv.mean(dim=1, keepdim=True)) / (
-            adv.std(dim=1, keepdim=True) + 1e-10
-        )
+        keys = ["obs", "acts", "logp", "rtgs", "adv"]
+        if self.gae_lambda is not None:
+            ep_len = out["ep_len"]
+            ep_lens = [
+                min(ep_len, M - s) for s in range(0, M, ep_len)
+            ]
+            adv, vtarg = self._gae(v, out["rews"], ep_lens)
+            if vtarg is not None:
+                out["vtarg"] = vtarg.reshape(-1)
+                keys.append("vtarg")
+        else:
+            adv = rtgs - v
+            adv = (adv - adv.mean(dim=1, keepdim=True)) / (
+                adv.std(dim=1, keepdim=True) + 1e-10
+            )
         out["adv"] = adv.reshape(-1)
         self.device_buf = out
         self.buf = {
-            i: {
-                k: out[k][i * M:(i + 1) * M]
-                for k in ("obs", "acts", "logp", "rtgs", "adv")
-            }
+            i: {k: out[k][i * M:(i + 1) * M] for k in keys}
             for i in range(N)
         }
+        for i in range(N):
+            self.buf[i]["rews"] = out["rews"]  # one team reward row
 
     # ------------------------------------------------------------------
     def local_batch_loss(self, i):
@@ -296,7 +393,10 @@ class DistPPOProblem:
         s2 = torch.clamp(ratios, 1 - clip, 1 + clip) * b["adv"]
         actor_loss = -torch.min(s1, s2).mean()
         v = self.critics[i](b["obs"]).squeeze(-1)
-        critic_loss = torch.nn.functional.mse_loss(v, b["rtgs"])
+        # critic_target "lambda" carries the lambda-returns as "vtarg"
+        critic_loss = torch.nn.functional.mse_loss(
+            v, b.get("vtarg", b["rtgs"])
+        )
         return actor_loss + self.conf["critic_coef"] * critic_loss
 
     # ------------------------------------------------------------------

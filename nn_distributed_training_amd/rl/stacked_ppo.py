@@ -174,11 +174,15 @@ class StackedPPOEngine:
         self.old_logp = cat("logp")
         self.rtgs = cat("rtgs")
         self.adv = cat("adv")
+        # the critic's target: the lambda-returns where the problem
+        # carries them (critic_target "lambda"), else the rewards-to-go
+        self.vtarg = cat("vtarg") if "vtarg" in buf[0] else self.rtgs
 
     def load_device_rollout(self, ro):
         """Adopt the ``[N*M, .]`` tensors of ``DeviceRollout.run`` as
-        they are (no copies; ``ro["adv"]`` once the problem has filled
-        it in - :meth:`values` needs the observations only)."""
+        they are (no copies; ``ro["adv"]``, and ``ro["vtarg"]`` under
+        ``critic_target: "lambda"``, once the problem has filled them in
+        - :meth:`values` needs the observations only)."""
         M = int(ro["M"])
         for key in ("obs", "acts", "logp", "rtgs"):
             t = ro[key]
@@ -188,6 +192,9 @@ class StackedPPOEngine:
         self.acts = ro["acts"]
         self.old_logp = ro["logp"]
         self.rtgs = ro["rtgs"]
+        self.vtarg = ro.get("vtarg", self.rtgs)
+        assert self.vtarg.shape == self.rtgs.shape
+        assert self.vtarg.is_contiguous() and self.vtarg.dtype == self.dtype
         if "adv" in ro:
             self.adv = ro["adv"].contiguous()
         if M != self.M:
@@ -255,7 +262,7 @@ class StackedPPOEngine:
         self._loss.zero_()
         self.ext.ppo_loss_bwd(
             mean, self.acts, self.old_logp, self.adv, v.reshape(-1),
-            self.rtgs, self._actor_bufs["dzs"][-1],
+            self.vtarg, self._actor_bufs["dzs"][-1],
             self._critic_bufs["dzs"][-1].reshape(-1), self._loss, self.M,
             float(conf["cov"]), float(conf["clip"]),
             float(conf["critic_coef"]), float(loss_scale),

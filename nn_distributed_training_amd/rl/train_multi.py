@@ -45,7 +45,7 @@ def default_conf(alg: str) -> dict:
     return conf
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--alg", default="dinno",
                    choices=["dinno", "cadmm", "dsgd", "dsgt"])
@@ -65,13 +65,35 @@ def main(argv=None):
              "a whole batch of episodes in one HIP kernel launch "
              "(device; needs a GPU; other action-noise stream than host)",
     )
-    args = p.parse_args(argv)
+    p.add_argument(
+        "--gae-lambda", type=float, default=None,
+        help="GAE(lambda) advantages with this lambda in [0, 1] "
+             "(default: the Monte-Carlo estimator rtg - V, GAE's "
+             "lambda = 1 corner)",
+    )
+    p.add_argument(
+        "--critic-target", default="rtg", choices=["rtg", "lambda"],
+        help="regress the critic on the rewards-to-go (rtg) or on the "
+             "lambda-returns (lambda; needs --gae-lambda)",
+    )
+    return p
 
-    torch.manual_seed(args.seed)
+
+def conf_from_args(args) -> dict:
     conf = default_conf(args.alg)
     conf["output_dir"] = args.out
     conf["grad_engine"] = args.grad_engine
     conf["rollout_engine"] = args.rollout_engine
+    conf["gae_lambda"] = args.gae_lambda
+    conf["critic_target"] = args.critic_target
+    return conf
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+
+    torch.manual_seed(args.seed)
+    conf = conf_from_args(args)
     if args.max_timesteps:
         conf["max_rl_timesteps"] = args.max_timesteps
 

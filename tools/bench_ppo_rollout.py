@@ -13,6 +13,12 @@ comparisons:
 * one whole DiNNO round, rollout() + step_round() with grad_engine
   "stacked", under the two rollout engines.
 
+With --gae-lambda LAM a third comparison times one device rollout()
+under the default Monte-Carlo advantages ("mc": the eager torch chain)
+against GAE(LAM) advantages ("gae": one ext.ppo_gae launch), the two
+alternating like the others; the first two comparisons stay on the
+default estimator.
+
 Every figure is a host clock around a window of calls that ends in a
 device synchronize, after untimed warm-up calls; the window is repeated
 --repeats times, the two variants alternating, and the median with the
@@ -42,7 +48,7 @@ from nn_distributed_training_amd.rl.envs import SimpleTagEnv  # noqa: E402
 from nn_distributed_training_amd.rl.ppo_optimizers import DiNNOPPO  # noqa: E402
 
 
-def make_optimizer(args, rollout_engine, device, seed=0):
+def make_optimizer(args, rollout_engine, device, seed=0, gae_lambda=None):
     torch.manual_seed(seed)
     env = SimpleTagEnv(num_predators=args.nodes, num_obstacles=2,
                        seed=seed)
@@ -50,7 +56,7 @@ def make_optimizer(args, rollout_engine, device, seed=0):
             "timesteps_per_batch": args.samples,
             "max_timesteps_per_episode": args.episode,
             "rollout_engine": rollout_engine,
-            "grad_engine": "stacked",
+            "grad_engine": "stacked", "gae_lambda": gae_lambda,
             "primal_iterations": args.primal_iterations,
             "rho_init": 0.3, "primal_lr_start": 1e-4,
             "primal_lr_finish": 1e-4, "lr_decay_type": "constant"}
@@ -118,6 +124,16 @@ def bench_dtype(dtype, args):
         "dinno_round_speedup": round(
             rd["host"][0] / rd["device"][0], 1),
     }
+    if args.gae_lambda is not None:
+        o_g = make_optimizer(args, "device", dev,
+                             gae_lambda=args.gae_lambda)
+        rg = compare({"mc": o_d.pr.rollout, "gae": o_g.pr.rollout},
+                     {"mc": args.iters, "gae": args.iters},
+                     {"mc": args.warmup, "gae": args.warmup},
+                     args.repeats)
+        out["gae_lambda"] = args.gae_lambda
+        out["rollout_device_estimator"] = {
+            k: row(x) for k, x in rg.items()}
     print(json.dumps(out), flush=True)
     return out
 
@@ -134,6 +150,9 @@ def main(argv=None):
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--repeats", type=int, default=5)
     p.add_argument("--dtypes", nargs="+", default=["float32", "float64"])
+    p.add_argument("--gae-lambda", type=float, default=None,
+                   help="also time the device rollout() with GAE(lambda) "
+                        "advantages against the default estimator")
     args = p.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("bench_ppo_rollout.py measures on the GPU; none found")

@@ -243,6 +243,71 @@ def test_stacked_density_matches_golden(alg):
 
 
 @requires_gpu
+@pytest.mark.parametrize("py_chain", ["0", "1"])
+@pytest.mark.parametrize("loss_name", ["MSELoss", "L1Loss"])
+def test_stacked_density_regression_loss_matches_golden(
+        loss_name, py_chain, monkeypatch):
+    """The density problem of test_stacked_density_matches_golden with
+    the MSE and L1 loss heads (regression_bwd + act_grad through the
+    output sigmoid), DSGD, through both the C++ backward chain
+    (loss_kind 2/3) and the python per-op branch. Sigmoid outputs never
+    equal the 0/1 targets, so the L1 gradient is defined everywhere."""
+    import numpy as np
+
+    from nn_distributed_training_amd.data.floorplan import (
+        synthetic_floorplan,
+    )
+    from nn_distributed_training_amd.data.lidar import (
+        Lidar2D,
+        RandomPoseLidarDataset,
+    )
+    from nn_distributed_training_amd.problems.dist_dense_problem import (
+        DistDensityProblem,
+    )
+
+    monkeypatch.setenv("NDTA_PY_CHAIN", py_chain)
+    torch.set_default_dtype(torch.float64)
+    conf = _conf(copy.deepcopy(ALG_CONFS["dsgd"]))
+
+    def build():
+        torch.manual_seed(7)
+        np.random.seed(7)
+        img = synthetic_floorplan(nx=96, ny=96, num_walls=3,
+                                  border_width=10, seed=0)
+        lidar = Lidar2D(img, 6, 0.25, 8, 1.0, 20, 3)
+        sets = [
+            RandomPoseLidarDataset(lidar, 4) for _ in range(N_NODES)
+        ]
+        val = RandomPoseLidarDataset(lidar, 4)
+        c = dict(conf, train_batch_size=len(sets[0]))
+        model = FourierNet([2, 16, 8, 1], scale=0.05)
+        return DistDensityProblem(
+            nx.cycle_graph(N_NODES), model,
+            getattr(torch.nn, loss_name)(), sets, val,
+            torch.device("cuda"), c,
+        ), c
+
+    pr_g, c = build()
+    opt_g = build_optimizer(pr_g, pr_g.device, c["optimizer_config"])
+    opt_g.train()
+    golden = pr_g.local_params_stack()
+
+    pr_s, c = build()
+    pr_s.stacked = StackedEngine(pr_s)
+    assert pr_s.stacked._use_chain == (py_chain == "0")
+    assert pr_s.stacked._loss_kind == loss_name
+    init = pr_s.stacked.theta.clone()
+    opt_s = build_optimizer(pr_s, pr_s.device, c["optimizer_config"])
+    opt_s.train()
+    assert not torch.allclose(pr_s.stacked.theta, init)  # it trained
+    print(f"density {loss_name} py_chain={py_chain} max|err| = "
+          f"{(pr_s.stacked.theta - golden).abs().max().item():.3e}")
+    torch.testing.assert_close(
+        pr_s.stacked.theta, golden, rtol=1e-8, atol=1e-8
+    )
+
+
+@requires_gpu
 @pytest.mark.parametrize("alg", ["dinno", "dsgt"])
 def test_stacked_checkpoint_resume(alg, tmp_path):
     torch.set_default_dtype(torch.float64)

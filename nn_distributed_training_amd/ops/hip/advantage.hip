@@ -6,10 +6,14 @@
 //
 // Node l owns rows [l*M, (l+1)*M) in the layout of rl/device_rollout.py:
 // uniform episodes of ep_len steps, the last one cut at M. A step s is
-// the last of its episode when (s+1) % ep_len == 0 or s+1 == M; an
-// episode's end is terminal (no bootstrap). With k_s = gamma*lambda, or 0
+// the last of its episode when (s+1) % ep_len == 0 or s+1 == M. By
+// default an episode's end is terminal (no bootstrap); with v_last
+// ([L*E], E = ceil(M / ep_len), row l*E + e: the critic's value of the
+// observation after episode e's last step) the end is a truncation and
+// the return goes on with gamma * v_last. With k_s = gamma*lambda, or 0
 // at an episode's last step,
-//   delta_s = r_s + gamma * V_{s+1} * [s not last] - V_s
+//   delta_s = r_s + gamma * V_{s+1} - V_s             s not last
+//   delta_s = r_s + gamma * v_last[l*E + e] - V_s     s last (0 if null)
 //   A_s     = delta_s + k_s * A_{s+1}
 //   ret_s   = A_s + V_s
 //   adv_s   = (A_s - mean A) / (std A + 1e-10)       std over M-1
@@ -26,7 +30,8 @@
 //   3  scans its chunk again from that value and keeps A_s.
 // The serial length is C, not ep_len or M. All arithmetic is double for
 // either T, the order of every sum is fixed (no atomics), the variance is
-// two-pass; T appears in the loads of v and the final stores only.
+// two-pass; T appears in the loads of v and v_last and the final stores
+// only.
 //
 // A_s stays in LDS for M <= LDS_MAX_M; above, `work` is a [L*M] double
 // row in global memory (the adv output itself when T is double), so M is
@@ -61,7 +66,8 @@ __global__ __launch_bounds__(BLOCK) void ppo_gae_k(
     T* adv,                             // [L*M]
     T* ret,                             // [L*M], may be null
     double* work,                       // [L*M] or null: A_s in LDS
-    int M, int ep_len, double gamma, double c) {
+    int M, int ep_len, double gamma, double c,
+    const T* __restrict__ v_last) {     // [L*E] or null: terminal ends
   __shared__ double s_a[NWAVE], s_p[NWAVE], s_part[NWAVE];
   extern __shared__ __align__(16) unsigned char gae_raw[];
 
@@ -72,11 +78,16 @@ __global__ __launch_bounds__(BLOCK) void ppo_gae_k(
   const double* rl = rews + (long)blockIdx.x * rew_stride;
   double* A = work != nullptr ? work + row
                               : reinterpret_cast<double*>(gae_raw);
+  const int E = (M + ep_len - 1) / ep_len;
+  const T* vend =
+      v_last != nullptr ? v_last + (long)blockIdx.x * E : nullptr;
 
   // TD residuals, one coalesced sweep
   for (int s = tid; s < M; s += BLOCK) {
     const bool last = s + 1 == M || (s + 1) % ep_len == 0;
-    const double vn = last ? 0.0 : (double)vl[s + 1];
+    const double vn =
+        !last ? (double)vl[s + 1]
+              : vend != nullptr ? (double)vend[s / ep_len] : 0.0;
     A[s] = rl[s] + gamma * vn - (double)vl[s];
   }
   __syncthreads();

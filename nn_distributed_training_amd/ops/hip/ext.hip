@@ -855,7 +855,8 @@ void ppo_loss_bwd(torch::Tensor mean, torch::Tensor acts,
 // constants in EnvParams order. Weights go to LDS where all N actors
 // fit beside the reward row, else they are read in place;
 // NDTA_ROLLOUT_WLDS=0/1 forces one or the other for A/B runs (1 only
-// where they fit).
+// where they fit). The optional last_obs [N*E, obs_dim] receives the
+// observation after every episode's last step (row l*E + e).
 void ppo_rollout(torch::Tensor theta, std::vector<long> in_dims,
                  std::vector<long> out_dims, std::vector<long> w_offs,
                  std::vector<long> b_offs, std::vector<long> act_ids,
@@ -864,7 +865,8 @@ void ppo_rollout(torch::Tensor theta, std::vector<long> in_dims,
                  torch::Tensor acts, torch::Tensor logp,
                  torch::Tensor rews, torch::Tensor rtgs,
                  torch::Tensor ep_rew, long M, long ep_len, double cov,
-                 double gamma, std::vector<double> envp) {
+                 double gamma, std::vector<double> envp,
+                 c10::optional<torch::Tensor> last_obs) {
   CHECK_DEV(theta); CHECK_DEV(resets); CHECK_DEV(obst); CHECK_DEV(eps);
   CHECK_DEV(obs); CHECK_DEV(acts); CHECK_DEV(logp); CHECK_DEV(rews);
   CHECK_DEV(rtgs); CHECK_DEV(ep_rew);
@@ -932,6 +934,13 @@ void ppo_rollout(torch::Tensor theta, std::vector<long> in_dims,
     TORCH_CHECK(t->scalar_type() == theta.scalar_type(),
                 "ppo_rollout tensors must share theta's dtype");
   }
+  if (last_obs.has_value()) {
+    CHECK_DEV(*last_obs);
+    TORCH_CHECK(last_obs->numel() == N * E * obs_dim &&
+                    last_obs->scalar_type() == theta.scalar_type(),
+                "ppo_rollout: last_obs must be [N*E, obs_dim] of theta's "
+                "dtype");
+  }
   rollout::EnvParams env{envp[0], envp[1], envp[2], envp[3], envp[4],
                          envp[5], envp[6], envp[7], envp[8], envp[9],
                          envp[10]};
@@ -966,7 +975,7 @@ void ppo_rollout(torch::Tensor theta, std::vector<long> in_dims,
           rews.data_ptr<double>(), rtgs.data_ptr<scalar_t>(),
           ep_rew.data_ptr<double>(), (int)N, (int)n_obst, (int)M,
           (int)ep_len, (scalar_t)std::sqrt(cov), (scalar_t)logc, gamma,
-          env);
+          env, opt_ptr<scalar_t>(last_obs));
     };
     if (wlds) launch(std::true_type{});
     else launch(std::false_type{});
@@ -978,13 +987,16 @@ void ppo_rollout(torch::Tensor theta, std::vector<long> in_dims,
 // ppo_gae_k, one block per node): v [L*M] of T, rews double, [M] with
 // rew_stride 0 (the device rollout's shared reward row) or [L*M] with
 // rew_stride M; adv and the optional ret (the lambda-returns) [L*M] of
-// T. Uniform episodes of ep_len steps, the last one cut at M. The
-// unnormalised advantages wait in LDS for the node's mean and std; above
+// T. Uniform episodes of ep_len steps, the last one cut at M; the
+// optional v_last [L*E] of T (E = ceil(M / ep_len), row l*E + e)
+// bootstraps every episode's end with gamma * v_last, and without it the
+// ends are terminal. The unnormalised advantages wait in LDS for the node's mean and std; above
 // LDS_MAX_M steps they wait in global memory instead: in adv itself
 // where T is double, else in a double row allocated here.
 void ppo_gae(torch::Tensor v, torch::Tensor rews, long rew_stride,
              torch::Tensor adv, c10::optional<torch::Tensor> ret, long M,
-             long ep_len, double gamma, double lam) {
+             long ep_len, double gamma, double lam,
+             c10::optional<torch::Tensor> v_last) {
   CHECK_DEV(v); CHECK_DEV(rews); CHECK_DEV(adv);
   TORCH_CHECK(M >= 2, "ppo_gae: M must be at least 2 (unbiased std)");
   TORCH_CHECK(M < (1L << 31) - advantage::BLOCK, "ppo_gae: M too large");
@@ -1018,6 +1030,13 @@ void ppo_gae(torch::Tensor v, torch::Tensor rews, long rew_stride,
                 "ppo_gae: ret must be [L*M] of v's dtype, apart from v "
                 "and adv");
   }
+  if (v_last.has_value()) {
+    CHECK_DEV(*v_last);
+    const long E = (M + ep_len - 1) / ep_len;
+    TORCH_CHECK(v_last->numel() == L * E &&
+                    v_last->scalar_type() == v.scalar_type(),
+                "ppo_gae: v_last must be [L*E] of v's dtype");
+  }
   const bool lds = M <= advantage::LDS_MAX_M;
   torch::Tensor work;
   if (!lds) {
@@ -1031,7 +1050,7 @@ void ppo_gae(torch::Tensor v, torch::Tensor rews, long rew_stride,
         cur_stream(), v.data_ptr<scalar_t>(), rews.data_ptr<double>(),
         rew_stride, adv.data_ptr<scalar_t>(), opt_ptr<scalar_t>(ret),
         lds ? nullptr : work.data_ptr<double>(), (int)M, (int)ep_len,
-        gamma, gamma * lam);
+        gamma, gamma * lam, opt_ptr<scalar_t>(v_last));
   });
   HIP_CHECK_LAST();
 }
@@ -1726,8 +1745,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("bce_bwd", &bce_bwd);
   mod.def("regression_bwd", &regression_bwd);
   mod.def("ppo_loss_bwd", &ppo_loss_bwd);
-  mod.def("ppo_rollout", &ppo_rollout);
-  mod.def("ppo_gae", &ppo_gae);
+  // the trailing optional outputs/inputs default to None, so the
+  // positional calls from before they existed keep working
+  namespace py = pybind11;
+  mod.def("ppo_rollout", &ppo_rollout, py::arg("theta"),
+          py::arg("in_dims"), py::arg("out_dims"), py::arg("w_offs"),
+          py::arg("b_offs"), py::arg("act_ids"), py::arg("resets"),
+          py::arg("obst"), py::arg("eps"), py::arg("obs"),
+          py::arg("acts"), py::arg("logp"), py::arg("rews"),
+          py::arg("rtgs"), py::arg("ep_rew"), py::arg("M"),
+          py::arg("ep_len"), py::arg("cov"), py::arg("gamma"),
+          py::arg("envp"), py::arg("last_obs") = py::none());
+  mod.def("ppo_gae", &ppo_gae, py::arg("v"), py::arg("rews"),
+          py::arg("rew_stride"), py::arg("adv"), py::arg("ret"),
+          py::arg("M"), py::arg("ep_len"), py::arg("gamma"),
+          py::arg("lam"), py::arg("v_last") = py::none());
   mod.def("feistel_perm", &feistel_perm);
   mod.def("consensus_cdist", &consensus_cdist);
   mod.def("fc_block", &fc_block);

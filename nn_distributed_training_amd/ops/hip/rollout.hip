@@ -21,6 +21,10 @@
 //      them, MPE integrator; the new state goes to the other state
 //      buffer, so one barrier ends the step
 // and after the last step a serial reverse scan gives the rewards-to-go.
+// With last_obs ([N*E, obs_dim], row l*E + e) the block also writes the
+// observation of the state its last step left, phase A's formula
+// (obs_element) once more: what env.step returned at the episode's end,
+// for partial-episode bootstrapping (rl/advantages.py).
 // The env state and all env arithmetic are double for either T: the
 // host env is double and casts only the observation.
 //
@@ -88,6 +92,23 @@ DEV_INLINE double team_reward(const double (*pos)[2], int N,
   return -0.1 * dsum + 10.0 * ncoll;
 }
 
+// Element c of predator i's observation in the state (pos, vel): the
+// layout of SimpleTagEnv._observations
+DEV_INLINE double obs_element(const double (*pos)[2],
+                              const double (*vel)[2], int N, int i,
+                              int c) {
+  const int d = c & 1;
+  if (c < 2) return vel[i][d];
+  if (c < 4) return pos[i][d];
+  if (c < 2 * N + 2) {
+    const int k = (c - 4) >> 1;
+    const int j = k < i ? k : k + 1;  // world order, self skipped
+    return pos[j][d] - pos[i][d];
+  }
+  if (c < 2 * N + 4) return pos[N][d] - pos[i][d];
+  return vel[N][d];
+}
+
 template <typename T, bool WLDS>
 __global__ void ppo_rollout_k(
     const T* __restrict__ theta, long n, Plan plan, int span, int W,
@@ -101,7 +122,8 @@ __global__ void ppo_rollout_k(
     T* __restrict__ rtgs,               // [N*M]
     double* __restrict__ ep_rew,        // [E]
     int N, int n_obst, int M, int ep_len, T sd, T logc, double gamma,
-    EnvParams env) {
+    EnvParams env,
+    T* __restrict__ last_obs) {         // [N*E, obs_dim], may be null
   __shared__ double s_pos[2][MAX_N + 1][2];
   __shared__ double s_vel[2][MAX_N + 1][2];
   __shared__ double s_obst[MAX_OBST][2];
@@ -140,21 +162,7 @@ __global__ void ppo_rollout_k(
     // ---- A: observations, and the reward of the step before
     if (tid < N * obs_dim) {
       const int i = tid / obs_dim, c = tid - i * obs_dim;
-      const int d = c & 1;
-      double o;
-      if (c < 2) {
-        o = s_vel[cur][i][d];
-      } else if (c < 4) {
-        o = s_pos[cur][i][d];
-      } else if (c < 2 * N + 2) {
-        const int k = (c - 4) >> 1;
-        const int j = k < i ? k : k + 1;  // world order, self skipped
-        o = s_pos[cur][j][d] - s_pos[cur][i][d];
-      } else if (c < 2 * N + 4) {
-        o = s_pos[cur][N][d] - s_pos[cur][i][d];
-      } else {
-        o = s_vel[cur][N][d];
-      }
+      const double o = obs_element(s_pos[cur], s_vel[cur], N, i, c);
       s_x[0][i][c] = (T)o;
       obs[((long)i * M + row0) * obs_dim + c] = (T)o;
     }
@@ -276,6 +284,14 @@ __global__ void ppo_rollout_k(
     cur ^= 1;
   }
 
+  // the observation the env returns after the episode's last step (the
+  // cut episode's too), for a caller that bootstraps truncated ends
+  if (last_obs != nullptr && tid < N * obs_dim) {
+    const int i = tid / obs_dim, c = tid - i * obs_dim;
+    const long E = gridDim.x;
+    last_obs[((long)i * E + e) * obs_dim + c] =
+        (T)obs_element(s_pos[cur], s_vel[cur], N, i, c);
+  }
   // the last step's reward, then rewards-to-go and the episode's sum
   if (tid == 0) {
     const double r = team_reward(s_pos[cur], N, env);

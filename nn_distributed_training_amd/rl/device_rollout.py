@@ -12,7 +12,10 @@ per episode - actor forward, Gaussian action, log-prob, prey heuristic,
 physics, reward, rewards-to-go - and writes the ``[N*M, .]`` tensors that
 ``StackedPPOEngine`` consumes: node ``l``'s step ``t`` of episode ``e`` is
 row ``l*M + e*ep_len + t``. ``rollout_engine: "device"`` of
-``DistPPOProblem`` selects it.
+``DistPPOProblem`` selects it. Every such end is a truncation, so the
+kernel also writes ``last_obs [N*E, obs_dim]``: row ``l*E + e`` is node
+``l``'s observation after episode ``e``'s last step, what ``env.step``
+returned there, for ``bootstrap_truncated`` (rl/advantages.py).
 
 The randomness comes in as tensors: reset positions drawn from
 ``env.rng`` in ``SimpleTagEnv.reset()``'s order (the env's stream is
@@ -120,7 +123,7 @@ def rollout_host_mirror(problem, resets, eps, M=None):
     obs_l = [[] for _ in range(N)]
     act_l = [[] for _ in range(N)]
     logp_l = [[] for _ in range(N)]
-    rews, rtgs, ep_rew = [], [], []
+    rews, rtgs, ep_rew, last = [], [], [], []
     for e in range(E):
         set_env_state(env, resets[e, :N], resets[e, N])
         obs = env._observations()
@@ -142,6 +145,8 @@ def rollout_host_mirror(problem, resets, eps, M=None):
             ep.append(float(r[0]))
         rews.extend(ep)
         ep_rew.append(float(sum(ep)))
+        # what the last step() returned: the observation after the end
+        last.append(torch.as_tensor(obs, dtype=dtype, device=pr.device))
         run, ep_rtgs = 0.0, []
         for r in reversed(ep):  # rollout()'s recursion
             run = r + gamma * run
@@ -157,6 +162,9 @@ def rollout_host_mirror(problem, resets, eps, M=None):
         ep_rew=torch.as_tensor(
             ep_rew, dtype=torch.float64, device=pr.device
         ),
+        # [E, N, obs_dim] -> row l*E + e
+        last_obs=torch.stack(last).transpose(0, 1).reshape(
+            N * E, -1).contiguous(),
         M=M, ep_len=ep_len,
     )
 
@@ -259,7 +267,9 @@ class DeviceRollout:
         """One batch of ``M`` steps with the actors of the ``[N, n]``
         stack ``theta``. Returns ``obs [N*M, obs_dim]``, ``acts [N*M,
         A]``, ``logp``/``rtgs [N*M]`` (engine dtype), ``rews [M]`` and
-        ``ep_rew [E]`` (double), plus ``M`` and ``ep_len``."""
+        ``ep_rew [E]`` (double), ``last_obs [N*E, obs_dim]`` (row ``l*E +
+        e``: the observation after episode ``e``'s last step), plus ``M``
+        and ``ep_len``."""
         M, ep_len, E = self.shape(M)
         N, dev, dt = self.N, self.device, self.dtype
         if theta.shape != (N, self.pr.n) or theta.dtype != dt:
@@ -282,13 +292,13 @@ class DeviceRollout:
             obs=mk(N * M, self.obs_dim), acts=mk(N * M, ACT_DIM),
             logp=mk(N * M), rews=mk(M, dtype=torch.float64),
             rtgs=mk(N * M), ep_rew=mk(E, dtype=torch.float64),
-            M=M, ep_len=ep_len,
+            last_obs=mk(N * E, self.obs_dim), M=M, ep_len=ep_len,
         )
         conf = self.pr.conf
         self.ext.ppo_rollout(
             theta.contiguous(), *self._plan, resets, self._obst, eps,
             out["obs"], out["acts"], out["logp"], out["rews"],
             out["rtgs"], out["ep_rew"], M, ep_len, float(conf["cov"]),
-            float(conf["gamma"]), self._envp,
+            float(conf["gamma"]), self._envp, out["last_obs"],
         )
         return out

@@ -18,6 +18,16 @@ its action noise comes from another random stream than
 above) switches the advantages to GAE(lambda) (rl/advantages.py), and
 ``critic_target: "lambda"`` (default ``"rtg"``) then regresses the critic
 on the lambda-returns instead of the rewards-to-go.
+
+``bootstrap_truncated`` (default ``False``: an episode's end counts as
+terminal, as in the reference) treats every episode end as what it is in
+this env, a time-limit truncation, and continues the return beyond it
+with ``gamma * V(o')``, the critic's value of the observation the env
+returned after the episode's last step (partial-episode bootstrapping,
+Pardo et al. 2018; rl/advantages.py has the formulas). The rewards-to-go,
+the advantages of either estimator and the lambda-returns all carry the
+tail; ``last_obs`` keeps those observations. It is an addition the
+reference does not have and consumes no randomness.
 """
 
 from __future__ import annotations
@@ -84,13 +94,19 @@ class DistPPOProblem:
         self.rollout_engine = self.conf.get("rollout_engine", "host")
         self.device_rollout = self._resolve_rollout_engine()
         self.device_buf = None
-        self.gae_lambda, self.critic_target = self._resolve_estimator()
+        (self.gae_lambda, self.critic_target,
+         self.bootstrap_truncated) = self._resolve_estimator()
+        # [N*E, obs_dim], row l*E + e: node l's observation after the
+        # last step of episode e of the latest rollout()
+        self.last_obs = None
 
     # ------------------------------------------------------------------
     def _resolve_estimator(self):
-        """``(gae_lambda, critic_target)`` of the config, checked."""
+        """``(gae_lambda, critic_target, bootstrap_truncated)`` of the
+        config, checked."""
         lam = self.conf.get("gae_lambda")
         target = self.conf.get("critic_target", "rtg")
+        boot = self.conf.get("bootstrap_truncated", False)
         if lam is not None:
             lam = float(lam)
             if not 0.0 <= lam <= 1.0:
@@ -106,13 +122,18 @@ class DistPPOProblem:
                 "critic_target='lambda' needs a gae_lambda: the "
                 "lambda-returns come from the GAE estimator"
             )
-        return lam, target
+        if not isinstance(boot, bool):
+            raise ValueError(
+                f"bootstrap_truncated must be True or False, got {boot!r}"
+            )
+        return lam, target, boot
 
-    def _gae(self, v, rews, ep_lens):
+    def _gae(self, v, rews, ep_lens, v_last=None):
         """GAE(lambda) from the critic values ``v [N, M]`` and the
         rewards (``[M]`` shared or ``[N, M]``, double): the normalised
         advantages and the critic target (None under ``"rtg"``), both
-        ``[N, M]`` of ``v``'s dtype. One ``ppo_gae`` launch where the
+        ``[N, M]`` of ``v``'s dtype. ``v_last [N, E]`` bootstraps the
+        episodes' ends (None: terminal). One ``ppo_gae`` launch where the
         extension is guaranteed (device rollout or stacked engine) and
         the episodes are uniform, the torch mirror otherwise."""
         from . import advantages as gae
@@ -126,11 +147,42 @@ class DistPPOProblem:
         )
         if have_ext and ep_len is not None:
             return gae.gae_advantages_hip(
-                v, rews, ep_len, gamma, lam, want_ret
+                v, rews, ep_len, gamma, lam, want_ret, v_last
             )
-        A, ret = gae.gae_advantages_torch(v, rews, ep_lens, gamma, lam)
+        A, ret = gae.gae_advantages_torch(
+            v, rews, ep_lens, gamma, lam, v_last
+        )
         adv = gae.normalize_advantages(A).to(v.dtype)
         return adv, ret.to(v.dtype) if want_ret else None
+
+    def _values_last(self, theta=None):
+        """``V_end [N, E]``: every node's critic on its rows of
+        ``self.last_obs``, with the parameters that give ``V(obs)`` for
+        the batch - the stacked engine's forward at ``theta`` (default:
+        the modules' parameters) where one is attached, else the critic
+        modules."""
+        N = self.N
+        if self.value_engine is not None:
+            eng = self.value_engine
+            if theta is None:
+                theta = eng.stack_from_modules()
+            return eng.values_last(theta, self.last_obs)
+        E = self.last_obs.shape[0] // N
+        with torch.no_grad():
+            return torch.stack([
+                self.critics[i](self.last_obs[i * E:(i + 1) * E])
+                .squeeze(-1)
+                for i in range(N)
+            ])
+
+    def _node_mc_adv(self, i):
+        """Node ``i``'s normalised Monte-Carlo advantages ``rtg - V(obs)``
+        from its critic module."""
+        b = self.buf[i]
+        with torch.no_grad():
+            v = self.critics[i](b["obs"]).squeeze(-1)
+        adv = b["rtgs"] - v
+        return (adv - adv.mean()) / (adv.std() + 1e-10)
 
     # ------------------------------------------------------------------
     def _resolve_rollout_engine(self):
@@ -206,7 +258,10 @@ class DistPPOProblem:
         keeps the per-step rewards (double). With ``gae_lambda`` the
         advantages are GAE(lambda) instead (``_finish_gae``), and
         ``critic_target: "lambda"`` adds the lambda-returns as
-        ``buf[i]["vtarg"]``.
+        ``buf[i]["vtarg"]``. With ``bootstrap_truncated`` the rewards-to-
+        go, and through them or through ``_gae`` the advantages and the
+        lambda-returns, go on beyond every episode's end with the
+        critic's value of ``last_obs``.
         """
         if self.device_rollout is not None:
             return self._rollout_device()
@@ -217,6 +272,7 @@ class DistPPOProblem:
         logp_buf = [[] for _ in range(self.N)]
         rews_eps = [[] for _ in range(self.N)]  # list of per-ep lists
         ep_total_rews = []
+        ep_last_obs = []  # per episode: what its last step() returned
 
         t = 0
         while t < T:
@@ -246,12 +302,21 @@ class DistPPOProblem:
                     break
             for i in range(self.N):
                 rews_eps[i].append(ep_rews[i])
+            ep_last_obs.append(nobs)
             ep_total_rews.append(
                 float(np.mean([sum(r) for r in ep_rews]))
             )
 
         self.total_timesteps += t
         self.ep_rew_history.append(float(np.mean(ep_total_rews)))
+        # [E, N, obs_dim] -> row l*E + e
+        self.last_obs = torch.as_tensor(
+            np.stack(ep_last_obs).swapaxes(0, 1).reshape(
+                self.N * len(ep_last_obs), -1),
+            dtype=torch.get_default_dtype(), device=self.device,
+        )
+        ep_lens = [len(ep) for ep in rews_eps[0]]
+        boot = self.bootstrap_truncated
 
         gamma = conf["gamma"]
         self.buf = {}
@@ -279,16 +344,26 @@ class DistPPOProblem:
                 obs=obs_i, acts=acts_i, logp=logp_i, rtgs=rtgs_i,
                 rews=rews_i,
             )
-            if self.gae_lambda is not None:
+            if self.gae_lambda is not None or boot:
                 continue
             if self.value_engine is None:
-                with torch.no_grad():
-                    v = self.critics[i](obs_i).squeeze(-1)
-                adv = rtgs_i - v
-                adv = (adv - adv.mean()) / (adv.std() + 1e-10)
-                self.buf[i]["adv"] = adv
+                self.buf[i]["adv"] = self._node_mc_adv(i)
+        v_last = None
+        if boot:
+            from .advantages import bootstrap_rtgs
+
+            v_last = self._values_last()
+            rtgs_b = bootstrap_rtgs(
+                torch.stack([self.buf[i]["rtgs"] for i in range(self.N)]),
+                v_last, ep_lens, gamma,
+            )
+            for i in range(self.N):
+                self.buf[i]["rtgs"] = rtgs_b[i]
         if self.gae_lambda is not None:
-            self._finish_gae([len(ep) for ep in rews_eps[0]])
+            self._finish_gae(ep_lens, v_last)
+        elif boot and self.value_engine is None:
+            for i in range(self.N):
+                self.buf[i]["adv"] = self._node_mc_adv(i)
         elif self.value_engine is not None:
             # V(obs) of all nodes from the stacked critic forward, then
             # the same per-node normalization batched over [N, M]
@@ -304,10 +379,11 @@ class DistPPOProblem:
             for i in range(self.N):
                 self.buf[i]["adv"] = adv[i]
 
-    def _finish_gae(self, ep_lens):
+    def _finish_gae(self, ep_lens, v_last=None):
         """``adv`` (and ``vtarg``) of a host rollout's buffers under
         ``gae_lambda``: V(obs) from the stacked engine where one is
-        attached, else from the critic modules."""
+        attached, else from the critic modules. ``v_last``: see
+        :meth:`_gae`."""
         N = self.N
         if self.value_engine is None:
             with torch.no_grad():
@@ -320,7 +396,7 @@ class DistPPOProblem:
             eng.load_obs([self.buf[i]["obs"] for i in range(N)])
             v = eng.values(eng.stack_from_modules())
         rews = torch.stack([self.buf[i]["rews"] for i in range(N)])
-        adv, vtarg = self._gae(v, rews, ep_lens)
+        adv, vtarg = self._gae(v, rews, ep_lens, v_last)
         for i in range(N):
             self.buf[i]["adv"] = adv[i]
             if vtarg is not None:
@@ -342,6 +418,9 @@ class DistPPOProblem:
         M = out["M"]
         self.total_timesteps += M
         self.ep_rew_history.append(float(out["ep_rew"].mean()))
+        self.last_obs = out["last_obs"]
+        ep_len = out["ep_len"]
+        ep_lens = [min(ep_len, M - s) for s in range(0, M, ep_len)]
 
         rtgs = out["rtgs"].view(N, M)
         if self.value_engine is None:
@@ -355,13 +434,18 @@ class DistPPOProblem:
             eng = self.value_engine
             eng.load_device_rollout(out)
             v = eng.values(theta)
+        v_last = None
+        if self.bootstrap_truncated:
+            from .advantages import bootstrap_rtgs
+
+            v_last = self._values_last(theta)
+            # in place: out["rtgs"] stays the tensor the engine adopted
+            rtgs.copy_(bootstrap_rtgs(
+                rtgs, v_last, ep_lens, float(self.conf["gamma"])
+            ))
         keys = ["obs", "acts", "logp", "rtgs", "adv"]
         if self.gae_lambda is not None:
-            ep_len = out["ep_len"]
-            ep_lens = [
-                min(ep_len, M - s) for s in range(0, M, ep_len)
-            ]
-            adv, vtarg = self._gae(v, out["rews"], ep_lens)
+            adv, vtarg = self._gae(v, out["rews"], ep_lens, v_last)
             if vtarg is not None:
                 out["vtarg"] = vtarg.reshape(-1)
                 keys.append("vtarg")

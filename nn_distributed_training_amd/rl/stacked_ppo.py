@@ -112,6 +112,8 @@ class StackedPPOEngine:
         self.theta = self.stack_from_modules()
         self.grad = torch.zeros_like(self.theta)
         self.M = None
+        # values_last()'s own activation rows, by E
+        self._last_bufs = {}
         self._loss = torch.zeros(
             self.N, 2, device=self.device, dtype=self.dtype
         )
@@ -211,12 +213,15 @@ class StackedPPOEngine:
             self._alloc(M)
 
     # ------------------------------------------------------------------
-    def _forward(self, plan, bufs, theta):
-        cur = self.obs
+    def _forward(self, plan, bufs, theta, x=None, rows=None):
+        """The net of ``plan`` on ``x`` (``rows`` rows per node), by
+        default on the loaded rollout's observations."""
+        cur = self.obs if x is None else x
+        rows = self.M if rows is None else rows
         for li, layer in enumerate(plan):
             out = bufs["acts"][li]
             self.ext.linear_fwd(
-                cur, theta, out, None, layer.w_off, layer.b_off, self.M,
+                cur, theta, out, None, layer.w_off, layer.b_off, rows,
                 layer.in_dim, layer.out_dim, ACT_IDS[layer.activation],
                 layer.scale,
             )
@@ -278,6 +283,37 @@ class StackedPPOEngine:
         theta = self._check_theta(theta)
         v = self._forward(self.critic_plan, self._critic_bufs, theta)
         return v.reshape(self.N, self.M).clone()
+
+    def values_last(self, theta, last_obs):
+        """Critic forward on the observations after the episodes' ends,
+        ``last_obs [N*E, obs_dim]`` (row ``l*E + e``, the layout of
+        ``DeviceRollout.run``): ``V_end`` as ``[N, E]``. The activations
+        go to small buffers of their own, so the loaded rollout, its
+        ``M``-row buffers and ``self.obs`` stay as they are.
+
+        ``linear_fwd`` picks its kernel from the row count: the MFMA and
+        the small-``I`` kernels want ``M >= 128`` / ``M >= 1024`` rows
+        and are never chosen for fewer; ``E`` rows per node down to 1
+        take the generic 16x16-tile kernel, which bounds-checks every
+        row, as does the MFMA kernel for an ``E`` of 128 and more."""
+        theta = self._check_theta(theta)
+        N = self.N
+        assert last_obs.dim() == 2 and last_obs.shape[0] % N == 0
+        E = last_obs.shape[0] // N
+        assert E >= 1 and last_obs.shape[1] == self.critic_plan[0].in_dim
+        x = last_obs.detach().to(self.device, self.dtype).contiguous()
+        if E not in self._last_bufs:
+            self._last_bufs[E] = {
+                "acts": [
+                    torch.empty(N * E, layer.out_dim, device=self.device,
+                                dtype=self.dtype)
+                    for layer in self.critic_plan
+                ]
+            }
+        v = self._forward(
+            self.critic_plan, self._last_bufs[E], theta, x=x, rows=E
+        )
+        return v.reshape(N, E).clone()
 
     def losses(self):
         """``[N, 2]`` (actor term, critic term) of the last

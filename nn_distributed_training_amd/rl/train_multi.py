@@ -76,6 +76,13 @@ def build_parser():
         help="regress the critic on the rewards-to-go (rtg) or on the "
              "lambda-returns (lambda; needs --gae-lambda)",
     )
+    p.add_argument(
+        "--bootstrap-truncated", action="store_true",
+        help="treat every episode end as the time-limit truncation it "
+             "is: continue returns and advantages beyond it with the "
+             "critic's value of the next observation (default: the end "
+             "counts as terminal)",
+    )
     return p
 
 
@@ -86,6 +93,7 @@ def conf_from_args(args) -> dict:
     conf["rollout_engine"] = args.rollout_engine
     conf["gae_lambda"] = args.gae_lambda
     conf["critic_target"] = args.critic_target
+    conf["bootstrap_truncated"] = args.bootstrap_truncated
     return conf
 
 

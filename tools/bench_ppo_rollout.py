@@ -19,6 +19,13 @@ against GAE(LAM) advantages ("gae": one ext.ppo_gae launch), the two
 alternating like the others; the first two comparisons stay on the
 default estimator.
 
+With --kernels the two kernels are timed on their own instead, launch
+by launch on fixed inputs: ext.ppo_rollout without ("off") and with
+("on") the last_obs output, and ext.ppo_gae without and with v_last.
+--off-only times the off launches alone: what a build from before
+these arguments existed can run, for a comparison against it (run the
+two trees' copies of this tool in turn, several times over).
+
 Every figure is a host clock around a window of calls that ends in a
 device synchronize, after untimed warm-up calls; the window is repeated
 --repeats times, the two variants alternating, and the median with the
@@ -138,6 +145,73 @@ def bench_dtype(dtype, args):
     return out
 
 
+def bench_kernels(dtype, args):
+    """ext.ppo_rollout and ext.ppo_gae alone, with and without the
+    bootstrap's output / input, on one batch's fixed inputs."""
+    from nn_distributed_training_amd.ops import get_ext
+
+    torch.set_default_dtype(dtype)
+    dev = torch.device("cuda")
+    pr = make_optimizer(args, "device", dev).pr
+    dr = pr.device_rollout
+    M, ep_len, E = dr.shape()
+    N = pr.N
+    theta = pr._theta_stack()
+    eps = dr.draw_noise(E, ep_len)
+    resets = torch.as_tensor(
+        dr.draw_resets(E), dtype=torch.float64).to(dev).contiguous()
+    out = dr.run(theta, resets.cpu().numpy(), eps)
+    conf = pr.conf
+    ext = get_ext()
+    names = ["off"] if args.off_only else ["off", "on"]
+
+    def rollout_fn(name):
+        tail = (out["last_obs"],) if name == "on" else ()
+
+        def fn():
+            ext.ppo_rollout(
+                theta, *dr._plan, resets, dr._obst, eps, out["obs"],
+                out["acts"], out["logp"], out["rews"], out["rtgs"],
+                out["ep_rew"], M, ep_len, float(conf["cov"]),
+                float(conf["gamma"]), dr._envp, *tail)
+        return fn
+
+    v = torch.randn(N * M, device=dev, dtype=dtype)
+    v_last = torch.randn(N * E, device=dev, dtype=dtype)
+    adv, ret = torch.empty_like(v), torch.empty_like(v)
+    lam = 0.95 if args.gae_lambda is None else args.gae_lambda
+
+    def gae_fn(name):
+        tail = (v_last,) if name == "on" else ()
+
+        def fn():
+            ext.ppo_gae(v, out["rews"], 0, adv, ret, M, ep_len,
+                        float(conf["gamma"]), lam, *tail)
+        return fn
+
+    iters = {k: args.kernel_iters for k in names}
+    warmup = {k: args.warmup for k in names}
+    ro = compare({k: rollout_fn(k) for k in names}, iters, warmup,
+                 args.repeats)
+    ga = compare({k: gae_fn(k) for k in names}, iters, warmup,
+                 args.repeats)
+
+    def row(x):
+        return {"median_us": round(x[0], 2), "min_us": round(x[1], 2),
+                "max_us": round(x[2], 2)}
+
+    res = {
+        "dtype": str(dtype).replace("torch.", ""), "nodes": N,
+        "timesteps_per_batch": M, "episode": ep_len,
+        "hidden": list(args.hidden), "iters": args.kernel_iters,
+        "repeats": args.repeats, "gae_lambda": lam,
+        "ppo_rollout_launch": {k: row(x) for k, x in ro.items()},
+        "ppo_gae_launch": {k: row(x) for k, x in ga.items()},
+    }
+    print(json.dumps(res), flush=True)
+    return res
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--nodes", type=int, default=3)
@@ -153,11 +227,21 @@ def main(argv=None):
     p.add_argument("--gae-lambda", type=float, default=None,
                    help="also time the device rollout() with GAE(lambda) "
                         "advantages against the default estimator")
+    p.add_argument("--kernels", action="store_true",
+                   help="time ext.ppo_rollout with/without last_obs and "
+                        "ext.ppo_gae with/without v_last instead")
+    p.add_argument("--kernel-iters", type=int, default=2000)
+    p.add_argument("--off-only", action="store_true",
+                   help="with --kernels: only the launches without the "
+                        "new arguments (all an older build can run)")
     args = p.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("bench_ppo_rollout.py measures on the GPU; none found")
     for name in args.dtypes:
-        bench_dtype(getattr(torch, name), args)
+        if args.kernels:
+            bench_kernels(getattr(torch, name), args)
+        else:
+            bench_dtype(getattr(torch, name), args)
 
 
 if __name__ == "__main__":

@@ -360,7 +360,10 @@ constexpr int FC_W2S = 65;  // padded LDS row stride of W2
 // block stamps wall_clock64() (100 MHz) at the phase boundaries into
 // fc_phase_stamps[block][slot]; ext.fc_phase_clock() reads them back.
 // The diagnostic build adds one barrier before the last stamp so slot 5
-// is the block's end, not wave 0's.
+// is the block's end, not wave 0's. fc_block_k: slots 0-5 bound P0..P4.
+// fc_fwd_split_k: 0 staged, 1 MFMA loop and slab stores issued, 2
+// ticket drawn (reducers only), 3 slabs summed and y1 in LDS, 4 P2
+// done, 5 P3 done.
 #ifdef NDTA_FC_PHASE_CLOCK
 constexpr int FC_CLK_BLOCKS = 256;
 __device__ unsigned long long fc_phase_stamps[FC_CLK_BLOCKS * 8];
@@ -373,9 +376,164 @@ __device__ unsigned long long fc_phase_stamps[FC_CLK_BLOCKS * 8];
       }                                                             \
     }                                                               \
   } while (0)
+// a block that runs no tail (fc_fwd_split_k's non-reducers) zeroes its
+// slot 2, so that the reader can tell this launch's reducers
+#define FC_STAMP_NONE(slot)                                         \
+  do {                                                              \
+    const int b_ = blockIdx.z * gridDim.x + blockIdx.x;             \
+    if (b_ < FC_CLK_BLOCKS) fc_phase_stamps[b_ * 8 + (slot)] = 0;   \
+  } while (0)
 #else
 #define FC_STAMP(slot) do {} while (0)
+#define FC_STAMP_NONE(slot) do {} while (0)
 #endif
+// W2 into its LDS image [16][FC_W2S] for the tail below: element t of
+// the [16 c][64 h] tile, a real zero where c >= C or h >= H (the tail's
+// MFMA operands sweep the whole tile, and 0 x stale LDS could be NaN).
+// The load is clamped, not branched, so it can sit in a batch of loads.
+template <typename T>
+DEV_INLINE T fc_w2_tile_load(const T* __restrict__ W2, int t, int H,
+                             int C) {
+  const int c = t >> 6, h = t & 63;
+  const T v = W2[min(c, C - 1) * H + min(h, H - 1)];
+  return (c < C && h < H) ? v : T(0);
+}
+
+// The fc2 tail of a 16-row tile, written once for fc_block_k and
+// fc_fwd_split_k: from y1 in LDS through the logits, log-softmax + NLL
+// and dZ2 (P2) to the dz1 store and the fc2 dW/db atomics (P3). Every
+// thread of the block calls it (it holds two barriers); waves 0-3 work.
+//
+// The three products are one 16x16 MFMA tile each per wave, 4 k-steps:
+//   logits Z[m][c]  = y1[m][:] . W2[c][:]   wave w sums h in [16w, 16w+16)
+//   dz1[m][h]       = dZ2[m][:] . W2[:][h]  wave w owns h-fragment 16w
+//   fc2 dW[c][h]    = dZ2[:][c] . y1[:][h]  wave w owns h-fragment 16w
+// The four partial logit tiles meet in zps and are added to b2 in wave
+// order, so the sum does not depend on timing. The operands sweep pad
+// rows and columns, which must be real zeros: W2 rows C..15 and columns
+// H..63 (fc_w2_tile_load), y1 columns H..63 (the caller's y1 store),
+// dZ2 columns C..15 (written here). Rows at or past M have dZ2 = 0, so
+// they add nothing to dW/db.
+//
+// LDS strides stay 65 (W2, y1) and 17 (dZ2, zps). A fragment read is
+// either lo * stride + lk (16 rows x 4 k) or lk * stride + lo (4 k x 16
+// columns), banked over 32 lanes (lk in {0,1} or {2,3}). With 17 both
+// forms have one colliding pair; with 65 both are 2-way (2 extra LDS
+// cycles per read, ~28 reads per wave). No stride clears both forms
+// (the first wants 2 mod 32, the second 16 mod 32), and 66 would only
+// move the conflict from the logits to the other two products.
+//
+// tgt_of(m) is row m's target; it is called only for rows below M.
+template <typename T, bool KEEP_DZ1, int SLOT_P2, typename TgtFn>
+DEV_INLINE void fc_tail(
+    const T* w2s,            // [16][FC_W2S] | b2 at [16 * FC_W2S]
+    const T* y1s,            // [16][65]
+    T* dz2s,                 // [16][17]
+    T* zps,                  // [4][16][17] scratch
+    T* dz1s,                 // [16][65] dz1 kept in LDS (KEEP_DZ1)
+    TgtFn tgt_of,
+    T* __restrict__ grad_l,  // the node's grad slice
+    T* __restrict__ dz1t,    // the tile's first dz1 row
+    T* __restrict__ loss_l,  // nullable
+    long w2_off, long b2_off, int m0, int M, int H, int C,
+    T loss_scale) {
+  using MF = gmfma::mfma_t<T>;
+  using acc_t = typename MF::acc_t;
+  constexpr int RT = FC_RT;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int lo = lane & 15;
+  const int lk = lane >> 4;
+  const bool work = wid < 4;  // wave-uniform
+  const int h0 = wid * 16;
+
+  // P2: fc2 logits, this wave's quarter of the contraction
+  if (work) {
+    acc_t z = {};
+    const T* Ar = y1s + lo * 65 + h0 + lk;      // y1[m = lo][h]
+    const T* Br = w2s + lo * FC_W2S + h0 + lk;  // W2[c = lo][h]
+#pragma unroll
+    for (int kk = 0; kk < 16; kk += 4) z = MF::mma(Ar[kk], Br[kk], z);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      zps[wid * (RT * 17) + MF::acc_row(lane, r) * 17 + lo] = z[r];
+    }
+  }
+  __syncthreads();
+
+  // log-softmax + NLL dZ2, one (row, class) per thread: row m's classes
+  // sit in 16 adjacent lanes, so the row max and the row sum are 4
+  // xor-shuffles each and every exp runs once.
+  if (work) {
+    const int m = tid >> 4, c = tid & 15;
+    const bool act = c < C;
+    const bool rowok = (m0 + m) < M;
+    T z = -INFINITY;
+    if (act) {
+      z = w2s[16 * FC_W2S + c];  // b2
+#pragma unroll
+      for (int w = 0; w < 4; ++w) z += zps[w * (RT * 17) + m * 17 + c];
+    }
+    T mx = z;
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) {
+      const T o = __shfl_xor(mx, off, 16);
+      mx = o > mx ? o : mx;
+    }
+    const T e = act ? ::exp(z - mx) : T(0);
+    T sum = e;
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) {
+      sum += __shfl_xor(sum, off, 16);
+    }
+    T dz = T(0);
+    if (act && rowok) {
+      const int tgt = tgt_of(m);
+      dz = (e / sum - (c == tgt ? T(1) : T(0))) * (loss_scale / T(M));
+      if (c == tgt && loss_l != nullptr) {
+        const T lse = mx + ::log(sum);
+        atomicAdd(loss_l, -(z - lse) / T(M));
+      }
+    }
+    dz2s[m * 17 + c] = dz;  // pad classes too: an MFMA operand
+  }
+  __syncthreads();
+  FC_STAMP(SLOT_P2);
+
+  // P3: dz1 = (dZ2 @ W2) * relu'(y1) -> global (and LDS for a caller
+  // that goes on to dX0); fc2 dW/db
+  if (work) {
+    acc_t d1 = {}, dw = {};
+    const T* A1 = dz2s + lo * 17 + lk;           // dZ2[m = lo][c]
+    const T* B1 = w2s + lk * FC_W2S + h0 + lo;   // W2[c][h]
+    const T* A2 = dz2s + lk * 17 + lo;           // dZ2[m][c = lo]
+    const T* B2 = y1s + lk * 65 + h0 + lo;       // y1[m][h]
+#pragma unroll
+    for (int kk = 0; kk < 16; kk += 4) {
+      d1 = MF::mma(A1[kk], B1[kk * FC_W2S], d1);
+      dw = MF::mma(A2[kk * 17], B2[kk * 65], dw);
+    }
+    const int h = h0 + lo;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = MF::acc_row(lane, r);  // m of d1, c of dw
+      const T v = y1s[row * 65 + h] > T(0) ? d1[r] : T(0);
+      if (KEEP_DZ1) dz1s[row * 65 + h] = v;  // 0 where h >= H
+      if (m0 + row < M && h < H) dz1t[(long)row * H + h] = v;
+      if (row < C && h < H) {
+        atomicAdd(&grad_l[w2_off + row * H + h], dw[r]);
+      }
+    }
+  }
+  if (tid >= 32 && tid < 32 + C) {
+    const int c = tid - 32;
+    T s = T(0);
+    for (int m = 0; m < RT; ++m) s += dz2s[m * 17 + c];
+    atomicAdd(&grad_l[b2_off + c], s);
+  }
+}
+
 // fc_block_k: the whole block as ONE launch, one 512-thread block per
 // row tile. Kept for stacks with so many row tiles that the split
 // forward's grid would pass the CU count (ext.hip fc_kernel_for).
@@ -443,9 +601,10 @@ __global__ __launch_bounds__(512) void fc_block_k(
   const T* x0b = x0 + (long)(l * (long)M + m0) * I;  // block's rows
 
   FC_STAMP(0);
-  // P0: W2 (row stride 65: the logit dots walk it by class) + b2
-  for (int t = tid; t < C * H; t += 512) {
-    w2s[(t / H) * FC_W2S + t % H] = th[w2_off + t];
+  // P0: W2 as the tail's zero-padded [16][64] tile (row stride 65) + b2
+  for (int t = tid; t < 16 * 64; t += 512) {
+    w2s[(t >> 6) * FC_W2S + (t & 63)] =
+        fc_w2_tile_load(th + w2_off, t, H, C);
   }
   for (int t = tid; t < C; t += 512) {
     w2s[16 * FC_W2S + t] = th[b2_off + t];
@@ -563,111 +722,33 @@ __global__ __launch_bounds__(512) void fc_block_k(
   ldstrip(wid, sa);
   ldstrip(wid + 8, sb);
 
-  // y1 = relu(z1 + b1) into LDS (never stored to HBM)
-  if (!producer && o0w < H) {
+  // y1 = relu(z1 + b1) into LDS (never stored to HBM), a real zero in
+  // the columns past H: the tail's MFMA operands sweep all 64
+  if (!producer) {
+    const int o = o0w + lo;
+    const T bo = b1[min(o, H - 1)];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int m = MF::acc_row(lane, r);
-      const int o = o0w + lo;
-      const T z = a1[r] + b1[o];
-      y1s[m * 65 + o] = z > T(0) ? z : T(0);
+      const T z = a1[r] + bo;
+      y1s[m * 65 + o] = (o < H && z > T(0)) ? z : T(0);
     }
   }
   __syncthreads();
   FC_STAMP(2);
 
-  // P2: fc2 logits + log-softmax + NLL dZ2, one (row, class) per
-  // thread: row m's classes sit in 16 adjacent lanes, so the row max
-  // and the row sum are 4 xor-shuffles each and every exp runs once.
-  if (tid < RT * 16) {  // waves 0-3, wave-uniform
-    const int m = tid >> 4, c = tid & 15;
-    const bool act = c < C;
-    const bool rowok = (m0 + m) < M;
-    T z = -INFINITY;
-    if (act) {
-      z = w2s[16 * FC_W2S + c];  // b2
-      if (H == 64) {  // 8 partial sums so the LDS loads batch
-        T part[8] = {};
-#pragma unroll
-        for (int hq = 0; hq < 8; ++hq) {
-#pragma unroll
-          for (int hh = 0; hh < 8; ++hh) {
-            const int h = hq * 8 + hh;
-            part[hh] += y1s[m * 65 + h] * w2s[c * FC_W2S + h];
-          }
-        }
-#pragma unroll
-        for (int hh = 0; hh < 8; ++hh) z += part[hh];
-      } else {
-        for (int h = 0; h < H; ++h) {
-          z += y1s[m * 65 + h] * w2s[c * FC_W2S + h];
-        }
-      }
-    }
-    T mx = z;
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-      const T o = __shfl_xor(mx, off, 16);
-      mx = o > mx ? o : mx;
-    }
-    const T e = act ? ::exp(z - mx) : T(0);
-    T sum = e;
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-      sum += __shfl_xor(sum, off, 16);
-    }
-    if (act) {
-      T dz = T(0);
-      if (rowok) {
-        const int tgt = (int)
+  // P2 + P3: the shared fc2 tail (waves 0-3); its logit partials use
+  // the stream's B buffers, free since P1's last barrier. dz1 stays in
+  // LDS for P4, zero in the pad columns the dX0 MFMA sweeps over.
+  fc_tail<T, true, 3>(
+      w2s, y1s, dz2s, Bs, dz1s,
+      [&](int m) {
+        return (int)
             Y_all[l * maxlen + idx[l * idx_stride + idx_off + m0 + m]];
-        dz = (e / sum - (c == tgt ? T(1) : T(0))) *
-             (loss_scale / T(M));
-        if (c == tgt && loss != nullptr) {
-          const T lse = mx + ::log(sum);
-          atomicAdd(&loss[l], -(z - lse) / T(M));
-        }
-      }
-      dz2s[m * 17 + c] = dz;
-    }
-  }
-  __syncthreads();
-  FC_STAMP(3);
-
-  // P3: dz1 = (dz2 @ W2) * relu'(y1) -> LDS + global (fc1 dW/db run
-  // on the store-path dw kernel); fc2 dW/db
-  for (int t = tid; t < RT * H; t += 512) {
-    const int m = t / H, h = t % H;
-    T s = T(0);
-    for (int c = 0; c < C; ++c) {
-      s += dz2s[m * 17 + c] * w2s[c * FC_W2S + h];
-    }
-    const T v = y1s[m * 65 + h] > T(0) ? s : T(0);
-    dz1s[m * 65 + h] = v;
-    if (m0 + m < M) {
-      dz1g[(long)(l * (long)M + m0 + m) * H + h] = v;
-    }
-  }
-  if (H < 64) {  // zero the pad columns the dX0 MFMA sweeps over
-    for (int t = tid; t < RT * (64 - H); t += 512) {
-      const int m = t / (64 - H), h = H + t % (64 - H);
-      dz1s[m * 65 + h] = T(0);
-    }
-  }
-  for (int t = tid; t < C * H; t += 512) {
-    const int c = t / H, h = t % H;
-    T s = T(0);
-    for (int m = 0; m < RT; ++m) {
-      s += dz2s[m * 17 + c] * y1s[m * 65 + h];
-    }
-    atomicAdd(&grad[l * n + w2_off + c * H + h], s);
-  }
-  if (tid >= 32 && tid < 32 + C) {
-    const int c = tid - 32;
-    T s = T(0);
-    for (int m = 0; m < RT; ++m) s += dz2s[m * 17 + c];
-    atomicAdd(&grad[l * n + b2_off + c], s);
-  }
+      },
+      grad + l * n, dz1g + (long)(l * (long)M + m0) * H,
+      loss != nullptr ? loss + l : nullptr, w2_off, b2_off, m0, M, H, C,
+      loss_scale);
   __syncthreads();
   FC_STAMP(4);
 
@@ -720,6 +801,8 @@ constexpr int FCS_DZ2 = FCS_Y1 + FC_RT * 65;       // [16][17]
 constexpr int FCS_FLAG = FCS_DZ2 + FC_RT * 17;     // "I am last" word
 constexpr int FCS_STG = 2424;                      // 16-byte multiple
 static_assert(FCS_FLAG + 2 <= FCS_STG, "fc split arena overlap");
+// the tail's logit partials reuse the operand image (KSP >= 34)
+static_assert(4 * FC_RT * 17 <= (FC_RT + 64) * 34, "fc split zps");
 constexpr int FCS_ROWS = FC_RT + 64;               // image rows
 constexpr int FCS_NLD = 18;  // staging loads in flight per thread
 
@@ -808,7 +891,7 @@ __global__ __launch_bounds__(256) void fc_fwd_split_k(
   T w2v[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    w2v[j] = th[w2_off + min(tid + j * 256, C * H - 1)];
+    w2v[j] = fc_w2_tile_load(th + w2_off, tid + j * 256, H, C);
   }
   const T b2v = th[b2_off + min(tid, C - 1)];
   const T b1v = th[b1_off + min(tid & 63, H - 1)];
@@ -857,12 +940,13 @@ __global__ __launch_bounds__(256) void fc_fwd_split_k(
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int t = tid + j * 256;
-    if (t < C * H) w2s[(t / H) * FC_W2S + t % H] = w2v[j];
+    const int t = tid + j * 256;  // the zero-padded [16][64] tile
+    w2s[(t >> 6) * FC_W2S + (t & 63)] = w2v[j];
   }
   if (tid < C) w2s[16 * FC_W2S + tid] = b2v;
   const int tgt = (int)Y_all[l * maxlen + trow];
   __syncthreads();
+  FC_STAMP(0);
 
   // this slice's share of z1: wave w owns o-fragment [16w, 16w+16);
   // two accumulators halve the MFMA dependency chain
@@ -884,6 +968,7 @@ __global__ __launch_bounds__(256) void fc_fwd_split_k(
                  a0[r] + a1[r]);
     }
   }
+  FC_STAMP(1);
 
   // publish the slab and draw a ticket. The slab went out write-through
   // (slab_store), so there is no release fence: every wave drains its
@@ -903,10 +988,12 @@ __global__ __launch_bounds__(256) void fc_fwd_split_k(
                          __HIP_MEMORY_SCOPE_AGENT);
     }
     *lastf = last;
+    if (!last) FC_STAMP_NONE(2);
   }
   __syncthreads();
   if (!*lastf) return;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  FC_STAMP(2);
 
   // reducer: z1 = slabs summed in slice order (independent of arrival
   // order), y1 = relu(z1 + b1) into LDS (never stored to HBM)
@@ -938,89 +1025,20 @@ __global__ __launch_bounds__(256) void fc_fwd_split_k(
     }
   }
   __syncthreads();
+  FC_STAMP(3);
 
-  // P2: fc2 logits + log-softmax + NLL dZ2, one (row, class) per
-  // thread: row m's classes sit in 16 adjacent lanes, so the row max
-  // and the row sum are 4 xor-shuffles each and every exp runs once.
-  {
-    const int m = tid >> 4, c = tid & 15;
-    const bool act = c < C;
-    const bool rowok = (m0 + m) < M;
-    T z = -INFINITY;
-    if (act) {
-      z = w2s[16 * FC_W2S + c];  // b2
-      if (H == 64) {  // 8 partial sums so the LDS loads batch
-        T part[8] = {};
-#pragma unroll
-        for (int hq = 0; hq < 8; ++hq) {
-#pragma unroll
-          for (int hh = 0; hh < 8; ++hh) {
-            const int h = hq * 8 + hh;
-            part[hh] += y1s[m * 65 + h] * w2s[c * FC_W2S + h];
-          }
-        }
-#pragma unroll
-        for (int hh = 0; hh < 8; ++hh) z += part[hh];
-      } else {
-        for (int h = 0; h < H; ++h) {
-          z += y1s[m * 65 + h] * w2s[c * FC_W2S + h];
-        }
-      }
-    }
-    T mx = z;
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-      const T o = __shfl_xor(mx, off, 16);
-      mx = o > mx ? o : mx;
-    }
-    const T e = act ? ::exp(z - mx) : T(0);
-    T sum = e;
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-      sum += __shfl_xor(sum, off, 16);
-    }
-    if (act) {
-      T dz = T(0);
-      if (rowok) {
-        dz = (e / sum - (c == tgt ? T(1) : T(0))) *
-             (loss_scale / T(M));
-        if (c == tgt && loss != nullptr) {
-          const T lse = mx + ::log(sum);
-          atomicAdd(&loss[l], -(z - lse) / T(M));
-        }
-      }
-      dz2s[m * 17 + c] = dz;
-    }
-  }
+  // P2 + P3: the shared fc2 tail; its logit partials use the operand
+  // image, which no wave reads after the barrier before the ticket
+  fc_tail<T, false, 4>(
+      w2s, y1s, dz2s, stg, static_cast<T*>(nullptr),
+      [&](int) { return tgt; },
+      grad + l * n, dz1g + (long)(l * (long)M + m0) * H,
+      loss != nullptr ? loss + l : nullptr, w2_off, b2_off, m0, M, H, C,
+      loss_scale);
+#ifdef NDTA_FC_PHASE_CLOCK
   __syncthreads();
-
-  // P3: dz1 = (dz2 @ W2) * relu'(y1) -> global (fc_dx0_k and the fc1
-  // dW/db kernel read it); fc2 dW/db
-  for (int t = tid; t < RT * H; t += 256) {
-    const int m = t / H, h = t % H;
-    T s = T(0);
-    for (int c = 0; c < C; ++c) {
-      s += dz2s[m * 17 + c] * w2s[c * FC_W2S + h];
-    }
-    if (m0 + m < M) {
-      dz1g[(long)(l * (long)M + m0 + m) * H + h] =
-          y1s[m * 65 + h] > T(0) ? s : T(0);
-    }
-  }
-  for (int t = tid; t < C * H; t += 256) {
-    const int c = t / H, h = t % H;
-    T s = T(0);
-    for (int m = 0; m < RT; ++m) {
-      s += dz2s[m * 17 + c] * y1s[m * 65 + h];
-    }
-    atomicAdd(&grad[l * n + w2_off + c * H + h], s);
-  }
-  if (tid >= 32 && tid < 32 + C) {
-    const int c = tid - 32;
-    T s = T(0);
-    for (int m = 0; m < RT; ++m) s += dz2s[m * 17 + c];
-    atomicAdd(&grad[l * n + b2_off + c], s);
-  }
+  FC_STAMP(5);
+#endif
 }
 
 // dX0 = dz1 @ W1 with the conv relu' mask, one block per (16-column

@@ -255,6 +255,157 @@ DEV_INLINE T step_mul_add(T a, T b, T c) {
   return a * b + c;
 }
 
+// ---------------------------------------------------------------------
+// One element of a DiNNO primal step, written once for fused_step_dual_k
+// and for the backward launch that carries the step
+// (fused_mnist.hip dw_dx0_conv_bwd_k with STEP on). Three pieces, so a
+// caller can put its own work (a barrier, a dot product) between them:
+//   step_elem_load   the element's own loads;
+//   step_nbr_sum     dinno_dual_threg_k's CSR walk, in its order, the
+//                    neighbour's value coming from the caller's accessor
+//                    nbr(table_row, q);
+//   step_elem_apply  dual and s (DUAL), the penalty gradient, the
+//                    SGD/Adam/AdamW update with step_mul_add's rounding,
+//                    the isolated-node freeze, and every store.
+// DUAL: the step carries the round's dual ascent (duals and s are
+// written); otherwise both are read and the math is
+// fused_step_k<T, MODE, true>'s at nparts 1. theta_in and theta_out may
+// be one buffer (fused_step_dual_k, whose barrier orders the accesses)
+// or two: then a frozen element is copied across.
+template <typename T>
+struct step_args_t {
+  const T* theta_in;   // [L, n]
+  T* theta_out;        // [L, n]
+  const T* remote;     // [R-L, n] received rows (may be null)
+  const int* offs;     // [L+1]
+  const int* idx;      // CSR neighbor rows
+  const int* deg;      // [L]
+  T* duals;            // [L, n]
+  T* s;                // [L, n]
+  T* m;                // Adam state (null for SGD)
+  T* v;
+  T rho, lr, beta1, beta2, eps, wd, bc1, bc2;
+  long n;
+  int L;
+};
+
+template <typename T>
+struct step_ld_t {
+  T th, du, sv, m_prev, v_prev;
+};
+
+// load_mv false: the Adam moments count as zero and are not read
+template <typename T, bool DUAL>
+DEV_INLINE step_ld_t<T> step_elem_load(const step_args_t<T>& a, long t,
+                                       bool load_mv) {
+  step_ld_t<T> r;
+  r.th = a.theta_in[t];
+  r.du = a.duals[t];
+  r.sv = DUAL ? T(0) : a.s[t];
+  r.m_prev = T(0);
+  r.v_prev = T(0);
+  if (load_mv) {
+    r.m_prev = a.m[t];
+    r.v_prev = a.v[t];
+  }
+  return r;
+}
+
+// S[q] = sum over node l's neighbours, k ascending, of nbr(row, q), for
+// NQ elements of the node at once. Four neighbours' loads go out
+// together (clamped, and a clamped value is not added), so a node of
+// degree <= 4 is one round trip however many elements the thread holds.
+template <typename T, int NQ, typename NbrFn>
+DEV_INLINE void step_nbr_sum(const step_args_t<T>& a, int l, NbrFn nbr,
+                             T (&S)[NQ]) {
+  const int k0 = a.offs[l], k1 = a.offs[l + 1];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) S[q] = T(0);
+  for (int k = k0; k < k1; k += 4) {
+    T nv[4][NQ];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = a.idx[min(k + j, k1 - 1)];
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) nv[j][q] = nbr(r, q);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (k + j < k1) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) S[q] += nv[j][q];
+      }
+    }
+  }
+}
+
+// a neighbour's theta_in[e] from memory: a local row or a received one
+template <typename T>
+DEV_INLINE T step_nbr_global(const step_args_t<T>& a, int r, long e) {
+  return table_row(a.theta_in, a.remote, (long)a.L, a.n, r)[e];
+}
+
+DEV_INLINE float step_fma(float a, float b, float c) {
+  return __builtin_fmaf(a, b, c);
+}
+DEV_INLINE double step_fma(double a, double b, double c) {
+  return __builtin_fma(a, b, c);
+}
+
+// S is step_nbr_sum's result (unused unless DUAL), g the loss gradient.
+// Every rounding is written out, with contraction off: each fused
+// multiply-add below is one that dinno_dual_threg_k and fused_step_k
+// have as compiled, in fp32 and fp64. Left to the compiler the choice
+// depends on the code around the call (in the backward launch it packed
+// deg * th with 2 * rho into one two-wide fp32 multiply and left the
+// subtraction of s unfused), and the callers must agree bit for bit.
+template <typename T, int MODE, bool DUAL>
+DEV_INLINE void step_elem_apply(const step_args_t<T>& a,
+                                const step_ld_t<T>& in, T S, T g, int l,
+                                long t) {
+#pragma clang fp contract(off)
+  T th = in.th, du = in.du, sv = in.sv;
+  if (DUAL) {
+    // dual += rho * (deg * th - S);  s = (deg * th + S) / 2
+    const T dg = T(a.offs[l + 1] - a.offs[l]);
+    du = step_fma(a.rho, step_fma(dg, th, -S), du);
+    sv = step_fma(dg, th, S) * T(0.5);
+    a.duals[t] = du;
+    a.s[t] = sv;
+  }
+  // an isolated node is frozen, see fused_step_k
+  const int dl = a.deg[l];
+  if (dl == 0) {
+    if (a.theta_out != a.theta_in) a.theta_out[t] = th;
+    return;
+  }
+  // g += dual + 2 * rho * (deg * th - s)
+  g = g + step_fma(T(2) * a.rho, step_fma(T(dl), th, -sv), du);
+  if (MODE == 2) {  // SGD: th - lr * g
+    a.theta_out[t] = step_fma(-a.lr, g, th);
+    return;
+  }
+  if (MODE == 1) {  // AdamW decoupled weight decay: th -= lr * wd * th
+    th = step_fma(-(a.lr * a.wd), th, th);
+  } else if (a.wd != T(0)) {  // Adam L2: g += wd * th
+    g = step_fma(a.wd, th, g);
+  }
+  const T mt = step_mul_add(T(1) - a.beta1, g, a.beta1 * in.m_prev);
+  const T vt = step_mul_add(g, (T(1) - a.beta2) * g, a.beta2 * in.v_prev);
+  a.m[t] = mt;
+  a.v[t] = vt;
+  a.theta_out[t] = th - a.lr * (mt / a.bc1) / (::sqrt(vt / a.bc2) + a.eps);
+}
+
+// f(mode_c): the optimizer mode as a compile-time constant, for a kernel
+// that takes it as a run-time argument
+template <typename F>
+DEV_INLINE void step_mode_switch(int mode, F&& f) {
+  if (mode == 0) f(std::integral_constant<int, 0>{});
+  else if (mode == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 2>{});
+}
+
 template <typename T, int MODE, bool FIRST>
 __global__ void __launch_bounds__(STEP_DUAL_THREADS) fused_step_dual_k(
     T* __restrict__ theta,         // [L, n] in/out (the round-start
@@ -272,6 +423,9 @@ __global__ void __launch_bounds__(STEP_DUAL_THREADS) fused_step_dual_k(
   // FIRST: the Adam moments count as zero and are not read
   constexpr bool LOAD_MV = MODE != 2 && !FIRST;
   __shared__ T th_s[STEP_DUAL_THREADS];  // [L][columns]
+  const step_args_t<T> a{theta, theta, remote, offs, idx, deg, duals,
+                         s_out, m, v, rho, lr, beta1, beta2, eps, wd,
+                         bc1, bc2, n, L};
   const int cols = blockDim.x;
   const int c = threadIdx.x, l = threadIdx.y;
   for (long e0 = blockIdx.x * (long)cols; e0 < n;
@@ -280,52 +434,22 @@ __global__ void __launch_bounds__(STEP_DUAL_THREADS) fused_step_dual_k(
     const bool live = e < n;
     const long t = (long)l * n + e;
     // all of the thread's loads go out before the barrier waits on th
-    T th = T(0), du = T(0), g = T(0), m_prev = T(0), v_prev = T(0);
+    step_ld_t<T> in{T(0), T(0), T(0), T(0), T(0)};
+    T g = T(0);
     if (live) {
-      th = theta[t];
-      du = duals[t];
+      in = step_elem_load<T, true>(a, t, LOAD_MV);
       g = grad[t];
-      if (LOAD_MV) {
-        m_prev = m[t];
-        v_prev = v[t];
-      }
     }
-    th_s[l * cols + c] = th;
+    th_s[l * cols + c] = in.th;
     __syncthreads();  // the strip's theta is read; stores may follow
     if (live) {
-      // phase 1: dinno_dual_threg_k's CSR walk, in its order
-      const int k0 = offs[l], k1 = offs[l + 1];
-      T S = T(0);
-      for (int k = k0; k < k1; ++k) {
-        const int r = idx[k];
-        S += r < L ? th_s[r * cols + c] : remote[((long)r - L) * n + e];
-      }
-      const T dg = T(k1 - k0);
-      du += rho * (dg * th - S);
-      const T sv = (dg * th + S) * T(0.5);
-      duals[t] = du;
-      s_out[t] = sv;
+      // a neighbour that is a local row comes from LDS
+      T S[1];
+      step_nbr_sum<T, 1>(a, l, [&](int r, int) {
+        return r < L ? th_s[r * cols + c] : remote[((long)r - L) * n + e];
+      }, S);
       if (zero_grad) grad[t] = T(0);
-      // phase 2: fused_step_k's body (nparts 1, with penalty); an
-      // isolated node is frozen, see there
-      const int dl = deg[l];
-      if (dl != 0) {
-        g += du + T(2) * rho * (T(dl) * th - sv);
-        if (MODE == 2) {  // SGD
-          theta[t] = th - lr * g;
-        } else {
-          if (MODE == 1) {  // AdamW decoupled weight decay
-            th -= lr * wd * th;
-          } else if (wd != T(0)) {  // Adam L2
-            g += wd * th;
-          }
-          const T mt = step_mul_add(T(1) - beta1, g, beta1 * m_prev);
-          const T vt = step_mul_add(g, (T(1) - beta2) * g, beta2 * v_prev);
-          m[t] = mt;
-          v[t] = vt;
-          theta[t] = th - lr * (mt / bc1) / (::sqrt(vt / bc2) + eps);
-        }
-      }
+      step_elem_apply<T, MODE, true>(a, in, S[0], g, l, t);
     }
     __syncthreads();  // th_s is free for the next strip
   }

@@ -1105,12 +1105,19 @@ void dw_conv_bwd_idx(torch::Tensor dZ, torch::Tensor X,
 // (torch tensors must not be destroyed after the runtime at exit).
 struct FcSplitWs {
   torch::Tensor slabs, tickets;
+  // one int32 ticket per node for the backward launch that carries the
+  // primal step (dw_dx0_conv_bwd_k with STEP on), kept zero the same way
+  torch::Tensor step_tickets;
 };
+
+FcSplitWs& fc_ws_of(const torch::Tensor& like) {
+  static auto* ws = new std::map<int, FcSplitWs>();
+  return (*ws)[like.get_device()];
+}
 
 FcSplitWs& fc_split_ws(const torch::Tensor& like, long slab_elems,
                        long tiles) {
-  static auto* ws = new std::map<int, FcSplitWs>();
-  FcSplitWs& w = (*ws)[like.get_device()];
+  FcSplitWs& w = fc_ws_of(like);
   const long need = slab_elems * (long)like.element_size();
   if (!w.slabs.defined() || w.slabs.numel() < need) {
     w.slabs = torch::empty(
@@ -1275,15 +1282,101 @@ bool bwd_dx0_fused_for(long L, long M, long I, long H, long F, long K,
   return bwd_dx0_fused(L, M, I, H, F, K, IMG, elem_size);
 }
 
+// A DiNNO primal step's arguments, as fused_step_dual and fused_step
+// take them; `dual`: the step carries the round's dual ascent.
+struct StepArgs {
+  c10::optional<torch::Tensor> remote;
+  torch::Tensor offs, idx, deg, duals, s;
+  c10::optional<torch::Tensor> m, v;
+  double rho, lr, beta1, beta2, eps, wd;
+  long step_t, mode;
+  bool first_step, dual;
+};
+
+// today's step launch on theta, from a gradient in `grad`
+void step_unfused(const StepArgs& st, torch::Tensor theta,
+                  torch::Tensor grad);
+
+// Whether the backward launch of the conv -> fc1 model also takes the
+// DiNNO primal step that follows it (fused_mnist.hip dw_dx0_conv_bwd_k
+// with STEP on), from theta_in into a second buffer theta_out. This is
+// the only place the condition is written: the launch is the one
+// bwd_dx0_fused chooses, the gradient is a plain [L, n] stack (nparts 1)
+// and there are at most STEP_DUAL_LMAX local nodes, as for
+// step_dual_fused. NDTA_BWD_STEP=0 keeps the step a launch of its own
+// for A/B runs.
+inline bool bwd_step_fused(long L, long M, long I, long H, long F, long K,
+                           long IMG, long elem_size, long nparts) {
+  static const bool off = []() {
+    const char* e = getenv("NDTA_BWD_STEP");
+    return e && e[0] == '0';
+  }();
+  return !off && nparts == 1 && L <= ew::STEP_DUAL_LMAX &&
+         bwd_dx0_fused(L, M, I, H, F, K, IMG, elem_size);
+}
+
+bool bwd_step_fused_for(long L, long M, long I, long H, long F, long K,
+                        long IMG, long elem_size, long nparts) {
+  return bwd_step_fused(L, M, I, H, F, K, IMG, elem_size, nparts);
+}
+
+// the step's tensors against theta_in [L, n]; the kernel indexes all of
+// them with theta's (l, e)
+void check_bwd_step(const StepArgs& st, const torch::Tensor& theta_in,
+                    const torch::Tensor& theta_out, long w2_off,
+                    long b2_off, long H, long C) {
+  const long L = theta_in.size(0), n = theta_in.size(1);
+  const auto dt = theta_in.scalar_type();
+  CHECK_DEV(theta_out);
+  TORCH_CHECK(theta_out.scalar_type() == dt &&
+                  theta_out.numel() == L * n &&
+                  theta_out.data_ptr() != theta_in.data_ptr(),
+              "bwd step: theta_out must be a second [L, n] buffer");
+  for (const auto* t : {&st.duals, &st.s}) {
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->scalar_type() == dt && t->numel() == L * n,
+                "bwd step: duals and s must be [L, n] of theta's dtype");
+  }
+  for (const auto* t : {&st.offs, &st.idx, &st.deg}) {
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->scalar_type() == torch::kInt,
+                "bwd step: int32 offs, idx and deg expected");
+  }
+  TORCH_CHECK(st.offs.numel() == L + 1 && st.deg.numel() == L,
+              "bwd step: offs [L+1] and deg [L] expected");
+  for (const auto* t : {&st.remote, &st.m, &st.v}) {
+    TORCH_CHECK(!t->has_value() ||
+                    ((*t)->is_cuda() && (*t)->is_contiguous() &&
+                     (*t)->scalar_type() == dt),
+                "bwd step: remote, m and v must be contiguous on GPU, of "
+                "theta's dtype");
+  }
+  TORCH_CHECK(!st.remote.has_value() || st.remote->numel() % n == 0,
+              "bwd step: remote [R-L, n]");
+  TORCH_CHECK(st.mode == 2 ||
+                  (st.m.has_value() && st.v.has_value() &&
+                   st.m->numel() == L * n && st.v->numel() == L * n),
+              "bwd step: Adam modes need m and v [L, n]");
+  TORCH_CHECK(C >= 1 && w2_off >= 0 && w2_off + C * H <= n &&
+                  b2_off >= 0 && b2_off + C <= n,
+              "bwd step: fc2 slices must lie inside [0, n)");
+}
+
 // fc1 dW/db + dX0 + gather-sourced conv dW/db in ONE launch. Caller has
-// checked bwd_dx0_fused.
+// checked bwd_dx0_fused. With `step` (caller has checked bwd_step_fused)
+// the launch also takes that primal step from theta into *theta_out;
+// fc2's grad slices, which it then consumes, are [C, H] at w2_off and
+// [C] at b2_off.
 void launch_dw_dx0_conv_bwd(
     const torch::Tensor& dz1, const torch::Tensor& x0,
     const torch::Tensor& theta, const torch::Tensor& pidx,
     const torch::Tensor& X_all, const torch::Tensor& src_idx,
     long idx_stride, long idx_off, const torch::Tensor& gstack,
     long w1_off, long b1_off, long M, long I, long H, long cw_off,
-    long cb_off, long F, long K, long IMG) {
+    long cb_off, long F, long K, long IMG,
+    const StepArgs* step = nullptr,
+    const torch::Tensor* theta_out = nullptr, long w2_off = 0,
+    long b2_off = 0, long C = 0) {
   CHECK_DEV(dz1); CHECK_DEV(x0); CHECK_DEV(theta); CHECK_DEV(pidx);
   CHECK_DEV(X_all); CHECK_DEV(src_idx); CHECK_DEV(gstack);
   const long L = gstack.size(0), n = gstack.size(1);
@@ -1305,18 +1398,63 @@ void launch_dw_dx0_conv_bwd(
   const long n_dw = gx * gy * L;
   const long cv_gx = I / 16, cv_gy = (M + 63) / 64;
   const long n_cv = cv_gx * cv_gy * L;
+  int* tickets = nullptr;
+  if (step != nullptr) {
+    TORCH_CHECK(theta_out != nullptr, "bwd step: theta_out missing");
+    check_bwd_step(*step, theta, *theta_out, w2_off, b2_off, H, C);
+    FcSplitWs& ws = fc_ws_of(theta);
+    if (!ws.step_tickets.defined() || ws.step_tickets.numel() < L) {
+      ws.step_tickets = torch::zeros(
+          {std::max<long>(L, ew::STEP_DUAL_LMAX)},
+          theta.options().dtype(torch::kInt32));
+    }
+    tickets = ws.step_tickets.data_ptr<int>();
+  }
   DISPATCH_FT(dz1, {
-    dispatch_kmax(K, [&](auto kmax) {
-      hipLaunchKernelGGL(
-          (fmnist::dw_dx0_conv_bwd_k<scalar_t, decltype(kmax)::value>),
-          dim3(n_dw + n_cv), dim3(256), 0, cur_stream(),
-          dz1.data_ptr<scalar_t>(), x0.data_ptr<scalar_t>(), w1_off,
-          b1_off, (int)M, (int)I, (int)H, (int)gx, (int)gy,
-          theta.data_ptr<scalar_t>(), pidx.data_ptr<unsigned char>(),
-          X_all.data_ptr<scalar_t>(), cw_off, cb_off, (int)IMG,
-          (int)cv_gx, (int)cv_gy, (int)n_cv, src_idx.data_ptr<long>(),
-          idx_stride, idx_off, maxlen, gstack.data_ptr<scalar_t>(), n);
-    });
+    fmnist::bwd_step_t<scalar_t> sp{};
+    if (step != nullptr) {
+      const StepArgs& st = *step;
+      sp.a = {theta.data_ptr<scalar_t>(),
+              theta_out->data_ptr<scalar_t>(),
+              opt_ptr<scalar_t>(st.remote), st.offs.data_ptr<int>(),
+              st.idx.data_ptr<int>(), st.deg.data_ptr<int>(),
+              st.duals.data_ptr<scalar_t>(), st.s.data_ptr<scalar_t>(),
+              opt_ptr<scalar_t>(st.m), opt_ptr<scalar_t>(st.v),
+              (scalar_t)st.rho, (scalar_t)st.lr, (scalar_t)st.beta1,
+              (scalar_t)st.beta2, (scalar_t)st.eps, (scalar_t)st.wd,
+              (scalar_t)(1.0 - std::pow(st.beta1, (double)st.step_t)),
+              (scalar_t)(1.0 - std::pow(st.beta2, (double)st.step_t)),
+              n, (int)L};
+      sp.mode = (int)st.mode;
+      sp.load_mv = (st.mode != 2 && !st.first_step) ? 1 : 0;
+      sp.w2_off = w2_off;
+      sp.b2_off = b2_off;
+      sp.C = (int)C;
+      sp.F = (int)F;
+      sp.tickets = tickets;
+    }
+    const auto go = [&](auto step_c) {
+      dispatch_kmax(K, [&](auto kmax) {
+        hipLaunchKernelGGL(
+            (fmnist::dw_dx0_conv_bwd_k<scalar_t, decltype(kmax)::value,
+                                       decltype(step_c)::value>),
+            dim3(n_dw + n_cv), dim3(256), 0, cur_stream(),
+            dz1.data_ptr<scalar_t>(), x0.data_ptr<scalar_t>(), w1_off,
+            b1_off, (int)M, (int)I, (int)H, (int)gx, (int)gy,
+            theta.data_ptr<scalar_t>(), pidx.data_ptr<unsigned char>(),
+            X_all.data_ptr<scalar_t>(), cw_off, cb_off, (int)IMG,
+            (int)cv_gx, (int)cv_gy, (int)n_cv, src_idx.data_ptr<long>(),
+            idx_stride, idx_off, maxlen, gstack.data_ptr<scalar_t>(), n,
+            sp);
+      });
+    };
+    if (step == nullptr) {
+      go(std::integral_constant<int, fmnist::STEP_NONE>{});
+    } else if (step->dual) {
+      go(std::integral_constant<int, fmnist::STEP_DUAL>{});
+    } else {
+      go(std::integral_constant<int, fmnist::STEP_PLAIN>{});
+    }
   });
   HIP_CHECK_LAST();
 }
@@ -1492,6 +1630,103 @@ void fused_step_dual(torch::Tensor theta, torch::Tensor grad,
     });
   });
   HIP_CHECK_LAST();
+}
+
+void step_unfused(const StepArgs& st, torch::Tensor theta,
+                  torch::Tensor grad) {
+  if (st.dual) {
+    fused_step_dual(theta, grad, st.remote, st.offs, st.idx, st.deg,
+                    st.duals, st.s, st.m, st.v, st.rho, st.lr, st.beta1,
+                    st.beta2, st.eps, st.wd, st.step_t, st.mode,
+                    st.first_step, 1, true);
+  } else {
+    fused_step(theta, grad, st.duals, st.s, st.deg, st.m, st.v, st.rho,
+               st.lr, st.beta1, st.beta2, st.eps, st.wd, st.step_t,
+               st.mode, st.first_step, 1, true);
+  }
+}
+
+// dw_dx0_conv_bwd_idx followed by the DiNNO primal step on its gradient
+// (fused_step_dual where `dual`, else fused_step with the penalty; the
+// grad stack is cleared as it is consumed). Where bwd_step_fused says so
+// this is ONE launch that reads theta_in and writes the stepped theta to
+// theta_out, and the call returns true; the fc1 slice of gstack is then
+// never written. Elsewhere the two launches run as before, theta_in is
+// stepped in place, theta_out is not touched and the call returns false.
+// The conv and fc2 slices of gstack hold this iteration's sums on entry
+// (fc2's complete, conv's zero).
+bool dw_dx0_conv_bwd_step_idx(
+    torch::Tensor dz1, torch::Tensor x0, torch::Tensor theta_in,
+    torch::Tensor theta_out, torch::Tensor pidx, torch::Tensor X_all,
+    torch::Tensor src_idx, long idx_stride, long idx_off,
+    torch::Tensor gstack, long w1_off, long b1_off, long M, long I,
+    long H, long cw_off, long cb_off, long F, long K, long IMG,
+    long w2_off, long b2_off, long C,
+    c10::optional<torch::Tensor> remote, torch::Tensor offs,
+    torch::Tensor idx, torch::Tensor deg, torch::Tensor duals,
+    torch::Tensor s, c10::optional<torch::Tensor> m,
+    c10::optional<torch::Tensor> v, double rho, double lr, double beta1,
+    double beta2, double eps, double wd, long step_t, long mode,
+    bool first_step, bool dual) {
+  const StepArgs st{remote, offs, idx, deg, duals, s, m, v, rho, lr,
+                    beta1, beta2, eps, wd, step_t, mode, first_step, dual};
+  if (bwd_step_fused(theta_in.size(0), M, I, H, F, K, IMG,
+                     x0.element_size(), 1)) {
+    launch_dw_dx0_conv_bwd(dz1, x0, theta_in, pidx, X_all, src_idx,
+                           idx_stride, idx_off, gstack, w1_off, b1_off,
+                           M, I, H, cw_off, cb_off, F, K, IMG, &st,
+                           &theta_out, w2_off, b2_off, C);
+    return true;
+  }
+  dw_dx0_conv_bwd_idx(dz1, x0, theta_in, pidx, X_all, src_idx, idx_stride,
+                      idx_off, gstack, w1_off, b1_off, M, I, H, cw_off,
+                      cb_off, F, K, IMG);
+  step_unfused(st, theta_in, gstack);
+  return false;
+}
+
+// mnist_fwd_bwd on theta_in followed by the DiNNO primal step, as one
+// native call: three launches where bwd_step_fused says so (the backward
+// launch carries the step and writes theta_out; returns true), else
+// mnist_fwd_bwd's launches and the step launch on theta_in (theta_out is
+// not touched; returns false). Either way the grad stack is all zeros
+// afterwards if it was on entry. No loss output: the caller of a round
+// that tracks the training loss keeps the separate calls.
+bool mnist_fwd_bwd_step(
+    torch::Tensor X_all, torch::Tensor src_idx, long idx_stride,
+    long idx_off, torch::Tensor theta_in, torch::Tensor theta_out,
+    torch::Tensor Y_all, torch::Tensor x0, torch::Tensor pidx,
+    torch::Tensor grad, torch::Tensor dx0, torch::Tensor dz1g,
+    c10::optional<torch::Tensor> loss, long cw_off, long cb_off, long F,
+    long K, long IMG, long w1_off, long b1_off, long w2_off, long b2_off,
+    long M, long I, long H, long C, double loss_scale,
+    c10::optional<torch::Tensor> remote, torch::Tensor offs,
+    torch::Tensor idx, torch::Tensor deg, torch::Tensor duals,
+    torch::Tensor s, c10::optional<torch::Tensor> m,
+    c10::optional<torch::Tensor> v, double rho, double lr, double beta1,
+    double beta2, double eps, double wd, long step_t, long mode,
+    bool first_step, bool dual) {
+  const StepArgs st{remote, offs, idx, deg, duals, s, m, v, rho, lr,
+                    beta1, beta2, eps, wd, step_t, mode, first_step, dual};
+  if (!bwd_step_fused(theta_in.size(0), M, I, H, F, K, IMG,
+                      x0.element_size(), 1)) {
+    mnist_fwd_bwd(X_all, src_idx, idx_stride, idx_off, theta_in, Y_all,
+                  x0, pidx, grad, dx0, dz1g, loss, cw_off, cb_off, F, K,
+                  IMG, w1_off, b1_off, w2_off, b2_off, M, I, H, C,
+                  loss_scale);
+    step_unfused(st, theta_in, grad);
+    return false;
+  }
+  conv_pool_fwd_idx(X_all, src_idx, idx_stride, idx_off, theta_in, x0,
+                    pidx, cw_off, cb_off, M, F, K, IMG);
+  fc_block_launch(x0, theta_in, Y_all, src_idx, idx_stride, idx_off, grad,
+                  dx0, dz1g, loss, w1_off, b1_off, w2_off, b2_off, M, I,
+                  H, C, loss_scale, true, false);
+  launch_dw_dx0_conv_bwd(dz1g, x0, theta_in, pidx, X_all, src_idx,
+                         idx_stride, idx_off, grad, w1_off, b1_off, M, I,
+                         H, cw_off, cb_off, F, K, IMG, &st, &theta_out,
+                         w2_off, b2_off, C);
+  return true;
 }
 
 #ifdef NDTA_FC_PHASE_CLOCK
@@ -1769,6 +2004,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("bwd_dx0_fused_for", &bwd_dx0_fused_for);
   mod.def("step_dual_fused_for", &step_dual_fused_for);
   mod.def("fused_step_dual", &fused_step_dual);
+  mod.def("bwd_step_fused_for", &bwd_step_fused_for);
+  mod.def("dw_dx0_conv_bwd_step_idx", &dw_dx0_conv_bwd_step_idx);
+  mod.def("mnist_fwd_bwd_step", &mnist_fwd_bwd_step);
 #ifdef NDTA_FC_PHASE_CLOCK
   mod.def("fc_phase_clock", &fc_phase_clock);
 #endif

@@ -1294,7 +1294,139 @@ DEV_INLINE void dx0_conv_bwd_body(
 // the dW blocks fill in around and after them (12.6 us per call);
 // started last they wait for dW blocks to retire at two blocks per CU
 // and the launch is 16.9 us (profiles/README.md).
-template <typename T, int KMAX>
+//
+// STEP != 0: the launch also takes the DiNNO primal step that followed
+// it (ew::fused_step_dual_k, STEP_DUAL, or ew::fused_step_k with the
+// penalty, STEP_PLAIN), element for element what those kernels compute
+// (ew::step_elem_*). The step reads theta_in, which is `theta` here, and
+// writes theta_out, another buffer: nothing in the launch writes
+// theta_in, so the conv role's W1 reads and the dual ascent's reads of
+// the neighbours' round-start theta race with no store.
+//  * dW role: the thread that owns dW[o][i] (and the bias block's row 0
+//    for db[o]) never stores it. Its step loads go out with the staging
+//    loads, before the barrier; after the dot product it steps its
+//    element with g = acc. The fc1 slice of the grad stack is not
+//    touched and stays zero.
+//  * conv role: its atomics, and the fc block's for fc2 in the launch
+//    before, leave F*K*K + F + C*H + C sums in the grad stack. Every
+//    conv block drains its atomics, meets, and one lane draws a ticket
+//    for the node (fc_fwd_split_k's hand-off: relaxed agent-scope
+//    atomics, no spin-wait). The block that draws the node's last ticket
+//    reads those sums past its L1, zeroes them, steps their elements and
+//    returns the ticket to zero. No block waits for another.
+constexpr int STEP_NONE = 0, STEP_PLAIN = 1, STEP_DUAL = 2;
+
+template <typename T>
+struct bwd_step_t {
+  ew::step_args_t<T> a;
+  int mode;      // 0 Adam, 1 AdamW, 2 SGD
+  int load_mv;   // 0: the moments count as zero and are not read
+  long w2_off, b2_off;
+  int C, F;
+  int* tickets;  // [L], zero between launches
+};
+
+// the dW role's sink (gemm::linear_bwd_dw_sink_body) on the step path
+template <typename T, bool DUAL>
+struct dw_step_sink {
+  const bwd_step_t<T>& p;
+  long w_off, b_off;
+  int l, I;
+  ew::step_ld_t<T> in;
+  T S[1];
+
+  DEV_INLINE void fetch(long e) {
+    in = ew::step_elem_load<T, DUAL>(p.a, (long)l * p.a.n + e,
+                                     p.load_mv != 0);
+    if (DUAL) {
+      ew::step_nbr_sum<T, 1>(p.a, l, [&](int r, int) {
+        return ew::step_nbr_global(p.a, r, e);
+      }, S);
+    }
+  }
+  DEV_INLINE void apply(long e, T g) {
+    ew::step_mode_switch(p.mode, [&](auto mode_c) {
+      ew::step_elem_apply<T, decltype(mode_c)::value, DUAL>(
+          p.a, in, S[0], g, l, (long)l * p.a.n + e);
+    });
+  }
+  DEV_INLINE void prefetch(int o, int i, bool live) {
+    if (live) fetch(w_off + (long)o * I + i);
+  }
+  DEV_INLINE void weight(int o, int i, T acc) {
+    apply(w_off + (long)o * I + i, acc);
+  }
+  // one thread row of one block in gx: its loads are a trip of their own
+  DEV_INLINE void bias(int o, T s) {
+    fetch(b_off + o);
+    apply(b_off + o, s);
+  }
+};
+
+// The end of a conv-role block on the step path; every thread of the
+// block arrives. `flag` is an LDS word. H is fc1's width, so fc2's W is
+// [C][H].
+template <typename T, bool DUAL>
+DEV_INLINE void bwd_step_ticket_tail(
+    const bwd_step_t<T>& p, T* gstack, long cw_off, long cb_off, int KK,
+    int H, int l, int per_node, int tid, int* flag) {
+  constexpr int NQ = 3;  // elements per thread and trip: 728 at MNIST
+  // the atomics are out of this wave when vmcnt drains; see
+  // fc_fwd_split_k for why no fence is needed on either side
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    const int got = __hip_atomic_fetch_add(
+        &p.tickets[l], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = got == per_node - 1;
+    if (last) {
+      __hip_atomic_store(&p.tickets[l], 0, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    }
+    *flag = last;
+  }
+  __syncthreads();
+  if (!*flag) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  const int n0 = p.F * KK, n1 = n0 + p.F, n2 = n1 + p.C * H;
+  const int total = n2 + p.C;
+  const long n = p.a.n;
+  for (int u0 = tid; u0 < total; u0 += 256 * NQ) {
+    long e[NQ];
+    T g[NQ], S[NQ];
+    ew::step_ld_t<T> in[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int u = min(u0 + q * 256, total - 1);
+      e[q] = u < n0   ? cw_off + u
+             : u < n1 ? cb_off + (u - n0)
+             : u < n2 ? p.w2_off + (u - n1)
+                      : p.b2_off + (u - n2);
+      g[q] = slab_load(&gstack[(long)l * n + e[q]]);
+      in[q] = ew::step_elem_load<T, DUAL>(p.a, (long)l * n + e[q],
+                                          p.load_mv != 0);
+    }
+    if (DUAL) {
+      ew::step_nbr_sum<T, NQ>(p.a, l, [&](int r, int q) {
+        return ew::step_nbr_global(p.a, r, e[q]);
+      }, S);
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      if (u0 + q * 256 < total) {
+        const long t = (long)l * n + e[q];
+        gstack[t] = T(0);  // the next launch's atomics start from zero
+        ew::step_mode_switch(p.mode, [&](auto mode_c) {
+          ew::step_elem_apply<T, decltype(mode_c)::value, DUAL>(
+              p.a, in[q], S[q], g[q], l, t);
+        });
+      }
+    }
+  }
+}
+
+template <typename T, int KMAX, int STEP = STEP_NONE>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(2, 2))) void dw_dx0_conv_bwd_k(
     // dW role (and the tile's operands: dZ = dz1, X = x0)
@@ -1305,26 +1437,43 @@ __attribute__((amdgpu_waves_per_eu(2, 2))) void dw_dx0_conv_bwd_k(
     const T* __restrict__ X_all, long cw_off, long cb_off, int IMG,
     int cv_gx, int cv_gy, int n_cv, const long* __restrict__ src_idx,
     long idx_stride, long idx_off, long maxlen,
-    T* __restrict__ gstack, long n) {
+    T* __restrict__ gstack, long n,
+    bwd_step_t<T> sp) {  // read only where STEP != STEP_NONE
   constexpr int DW_LDS = 2 * gemm::DW_ROWS * (gemm::TILE + 1);
   constexpr int CV_LDS = (KMAX * KMAX + 1) * 4;
+  static_assert(STEP == STEP_NONE || CV_LDS + 2 <= DW_LDS,
+                "the ticket flag sits behind the conv role's wave sums");
   __shared__ T smem[DW_LDS > CV_LDS ? DW_LDS : CV_LDS];
   const int tid = threadIdx.x;
   if ((int)blockIdx.x < n_cv) {
     const int bid = blockIdx.x;
+    const int l = bid / (cv_gx * cv_gy);
     dx0_conv_bwd_body<T, KMAX>(
         X, theta, dZ, w_off, O, pidx, X_all, gstack, n, cw_off, cb_off,
         M, I, IMG, src_idx, idx_stride, idx_off, maxlen, bid % cv_gx,
-        (bid / cv_gx) % cv_gy, bid / (cv_gx * cv_gy), tid, smem);
+        (bid / cv_gx) % cv_gy, l, tid, smem);
+    if constexpr (STEP != STEP_NONE) {
+      bwd_step_ticket_tail<T, STEP == STEP_DUAL>(
+          sp, gstack, cw_off, cb_off, KMAX * KMAX, O, l, cv_gx * cv_gy,
+          tid, reinterpret_cast<int*>(smem + CV_LDS));
+    }
   } else {
     const int bid = blockIdx.x - n_cv;
     const int bx = bid % dw_gx;
     const int by = (bid / dw_gx) % dw_gy;
     const long bz = bid / (dw_gx * dw_gy);
-    gemm::linear_bwd_dw_body<T>(
-        dZ, X, gstack, n, w_off, b_off, M, I, O, bx, by, bz,
-        tid / gemm::TILE, tid % gemm::TILE, smem,
-        smem + gemm::DW_ROWS * (gemm::TILE + 1));
+    if constexpr (STEP != STEP_NONE) {
+      dw_step_sink<T, STEP == STEP_DUAL> sink{
+          sp, w_off, b_off, (int)bz, I, {}, {}};
+      gemm::linear_bwd_dw_sink_body<T>(
+          dZ, X, M, I, O, bx, by, bz, tid / gemm::TILE, tid % gemm::TILE,
+          smem, smem + gemm::DW_ROWS * (gemm::TILE + 1), sink);
+    } else {
+      gemm::linear_bwd_dw_body<T>(
+          dZ, X, gstack, n, w_off, b_off, M, I, O, bx, by, bz,
+          tid / gemm::TILE, tid % gemm::TILE, smem,
+          smem + gemm::DW_ROWS * (gemm::TILE + 1));
+    }
   }
 }
 

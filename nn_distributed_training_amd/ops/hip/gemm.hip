@@ -220,14 +220,33 @@ __global__ void linear_bwd_dx_k(
 // role of a flat grid; the summation order (m ascending per output
 // element; bias rows m = to, to+16, ... ascending, then to ascending)
 // is the same wherever it is called from.
+//
+// Where the results go is the caller's Sink:
+//   sink.prefetch(o, i, live)  once, after the first pass's global loads
+//                              have issued and before its barrier: loads
+//                              of the sink's own ride the same round trip;
+//   sink.weight(o, i, acc)     dW[o][i], from the owning thread, in range;
+//   sink.bias(o, s)            db[o], from the bias block's thread row 0.
+// dw_store_sink writes both into the grad stack.
 constexpr int DW_ROWS = 4 * TILE;
 
 template <typename T>
-DEV_INLINE void linear_bwd_dw_body(
+struct dw_store_sink {
+  T* __restrict__ gstack;
+  long n, w_off, b_off, l;
+  int I;
+  DEV_INLINE void prefetch(int, int, bool) {}
+  DEV_INLINE void weight(int o, int i, T acc) {
+    gstack[l * n + w_off + (long)o * I + i] = acc;
+  }
+  DEV_INLINE void bias(int o, T s) { gstack[l * n + b_off + o] = s; }
+};
+
+template <typename T, typename Sink>
+DEV_INLINE void linear_bwd_dw_sink_body(
     const T* __restrict__ dZ, const T* __restrict__ X,
-    T* __restrict__ gstack, long n, long w_off, long b_off,
     int M, int I, int O, int bx, int by, long bz, int to, int ti,
-    T* __restrict__ gs, T* __restrict__ xs) {
+    T* __restrict__ gs, T* __restrict__ xs, Sink& sink) {
   constexpr int TP = TILE + 1;
   const long l = bz;
   const T* dZl = dZ + l * (long)M * O;
@@ -259,6 +278,9 @@ DEV_INLINE void linear_bwd_dw_body(
         x[r] = (m < M && i_ld < I) ? Xl[m * I + i_ld] : T(0);
       }
     }
+    if (k0 == 0) {
+      sink.prefetch(o0 + to, i0 + ti, o0 + to < O && i0 + ti < I);
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       gs[(to + r * TILE) * TP + ti] = g[r];
@@ -272,9 +294,7 @@ DEV_INLINE void linear_bwd_dw_body(
     }
   }
   const int o = o0 + to, i = i0 + ti;
-  if (o < O && i < I) {
-    gstack[l * n + w_off + (long)o * I + i] = acc;
-  }
+  if (o < O && i < I) sink.weight(o, i, acc);
   if (bias_block) {
     // column-sum bacc over to (16 rows) through LDS, thread row 0 writes
     __syncthreads();  // gs is still being read by the last pass
@@ -284,9 +304,20 @@ DEV_INLINE void linear_bwd_dw_body(
       T s = T(0);
 #pragma unroll
       for (int r = 0; r < TILE; ++r) s += gs[r * TP + ti];
-      gstack[l * n + b_off + o0 + ti] = s;
+      sink.bias(o0 + ti, s);
     }
   }
+}
+
+template <typename T>
+DEV_INLINE void linear_bwd_dw_body(
+    const T* __restrict__ dZ, const T* __restrict__ X,
+    T* __restrict__ gstack, long n, long w_off, long b_off,
+    int M, int I, int O, int bx, int by, long bz, int to, int ti,
+    T* __restrict__ gs, T* __restrict__ xs) {
+  dw_store_sink<T> sink{gstack, n, w_off, b_off, bz, I};
+  linear_bwd_dw_sink_body<T>(dZ, X, M, I, O, bx, by, bz, to, ti, gs, xs,
+                             sink);
 }
 
 template <typename T>

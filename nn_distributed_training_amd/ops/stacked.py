@@ -29,6 +29,8 @@ from __future__ import annotations
 import os
 import time
 from collections import defaultdict
+from dataclasses import dataclass
+from typing import Optional
 
 import torch
 
@@ -307,6 +309,49 @@ class _OnlineWindowSampler:
         return self.buf, self.B
 
 
+@dataclass
+class PrimalStep:
+    """One DiNNO primal step for ``StackedEngine.train_step(step=...)``
+    to fold into the backward launch (ext.hip mnist_fwd_bwd_step). The
+    driver fills one per primal iteration. ``theta_in`` is read and
+    ``theta_out`` receives the stepped parameters; ``dual`` says the
+    step carries the round's dual ascent. On return ``taken`` is True
+    if the step was issued, and ``fused`` is True if it went into
+    ``theta_out`` (False: the old launches stepped ``theta_in`` in
+    place)."""
+
+    theta_in: torch.Tensor
+    theta_out: torch.Tensor
+    remote: Optional[torch.Tensor]
+    offs: torch.Tensor
+    idx: torch.Tensor
+    deg: torch.Tensor
+    duals: torch.Tensor
+    s: torch.Tensor
+    m: Optional[torch.Tensor]
+    v: Optional[torch.Tensor]
+    rho: float
+    lr: float
+    wd: float
+    step_t: int
+    mode: int
+    first_step: bool
+    dual: bool
+    beta1: float = 0.9
+    beta2: float = 0.999
+    eps: float = 1e-8
+    taken: bool = False
+    fused: bool = False
+
+    def native_args(self):
+        return (
+            self.remote, self.offs, self.idx, self.deg, self.duals,
+            self.s, self.m, self.v, self.rho, self.lr, self.beta1,
+            self.beta2, self.eps, self.wd, self.step_t, self.mode,
+            self.first_step, self.dual,
+        )
+
+
 class StackedEngine:
     def __init__(self, problem):
         self.ext = get_ext()
@@ -334,6 +379,12 @@ class StackedEngine:
         ]
         self.theta = torch.stack(rows).contiguous()
         self.grad = torch.zeros_like(self.theta)
+        # second parameter buffer for the rounds whose backward launch
+        # carries the primal step (DiNNOStackedDriver.step_round): the
+        # first iteration of a pair writes all of it before the second
+        # reads it, so nothing in it outlives a round and it is no part
+        # of any saved state
+        self.theta_alt = torch.empty_like(self.theta)
 
         self._stage_data()
         self.B = problem.conf["train_batch_size"]
@@ -641,9 +692,33 @@ class StackedEngine:
         )
 
     def fwd_bwd(self, xb, yb, loss_scale=1.0, want_loss=False,
-                graph_offs=None, pit=0):
+                graph_offs=None, pit=0, step=None):
         """Forward + backward for one primal iteration; takes the fused
-        fc-block path when the model/loss shape allows it."""
+        fc-block path when the model/loss shape allows it. With a
+        PrimalStep (fc-block path, no loss wanted) the same native call
+        takes that step as well and marks it taken."""
+        if step is not None:
+            assert graph_offs is None and not want_loss
+            assert self.fc_block_applicable()
+            bufs = self._bufs
+            conv, fc1, fc2 = self.spec.layers
+            idx_t, stride = self.sampler.index_ref()
+            if not self.grad_is_zero:
+                self.grad.zero_()
+            step.fused = self.ext.mnist_fwd_bwd_step(
+                self.X_all, idx_t, stride, self._last_off, step.theta_in,
+                step.theta_out, self.Y_all, bufs["acts"][0],
+                bufs["idxs"][0], self.grad, bufs["dzs"][0],
+                bufs["dzs"][1], None,
+                conv.w_off, conv.b_off, conv.out_dim, conv.kernel_size,
+                conv.in_dim, fc1.w_off, fc1.b_off, fc2.w_off, fc2.b_off,
+                self.B, fc1.in_dim, fc1.out_dim, fc2.out_dim, loss_scale,
+                *step.native_args(),
+            )
+            step.taken = True
+            # either path consumed the gradient and left the stack zero
+            self.grad_is_zero = True
+            return None
         if graph_offs is None and self.fc_block_applicable():
             bufs = self._bufs
             conv, fc1, fc2 = self.spec.layers
@@ -677,12 +752,20 @@ class StackedEngine:
             graph_offs=graph_offs, pit=pit,
         )
 
-    def train_step(self, want_loss=False):
+    def train_step(self, want_loss=False, step=None):
         """Draw the next batch and run forward + backward on it, by the
         megakernel where it is enabled, else by the layered path.
         Returns (loss or None, grad tensor, nparts): the megakernel
         leaves [L, nparts, n] per-tile slabs, the layered path
-        self.grad with nparts 1."""
+        self.grad with nparts 1. ``step``: a PrimalStep to take in the
+        same native call (the caller has checked that the fc-block path
+        applies); it comes back with ``taken`` set."""
+        if step is not None:
+            with _timer("next_batch"):
+                self.next_batch()
+            with _timer("fwd_bwd_step"):
+                self.fwd_bwd(None, None, step=step)
+            return None, self.grad, 1
         if self.fused_step_available():
             with _timer("train_step"):
                 lb = self.run_fused_mnist(
@@ -1207,6 +1290,34 @@ class DiNNOStackedDriver:
                 eng.theta, rbuf, offs, idx, self.duals, self.s, self.rho
             )
         want_tl = bool(getattr(pr, "track_tloss", False))
+        # The backward launch carries the primal step (ext.hip
+        # mnist_fwd_bwd_step) where the fc-block path runs and nothing
+        # else needs the grad stack. Each such step writes the other
+        # parameter buffer, so an even number of them ends in eng.theta:
+        # theta -> theta_alt (with the dual ascent), theta_alt -> theta.
+        # Where the native dispatch keeps the step a launch of its own
+        # it steps its input buffer in place, and the next iteration
+        # goes on from there.
+        if (
+            self.pits > 0 and self.pits % 2 == 0 and not want_tl
+            and not eng.fused_step_available()
+            and eng.fc_block_applicable()
+        ):
+            cur, other = eng.theta, eng.theta_alt
+            for pi in range(self.pits):
+                self.step_t += 1
+                st = PrimalStep(
+                    cur, other, rbuf, offs, idx, deg, self.duals, self.s,
+                    *mv, self.rho, lr, self.wd, self.step_t, self.mode,
+                    self.step_t == 1, pi == 0,
+                )
+                eng.train_step(step=st)
+                assert st.taken
+                if st.fused:
+                    cur, other = other, cur
+            # all fused or none: the dispatch does not change in a round
+            assert cur is eng.theta
+            return
         for pi in range(self.pits):
             wl = want_tl and pi == self.pits - 1
             lb, grad_t, nparts = eng.train_step(want_loss=wl)

@@ -7,6 +7,7 @@
 #include "elementwise.hip"
 #include "gemm.hip"
 #include "gemm_mfma.hip"
+#include "gemm_bf16.hip"
 #include "conv.hip"
 #include "losses.hip"
 #include "rollout.hip"
@@ -292,15 +293,41 @@ void axpy(torch::Tensor x, torch::Tensor g, double alpha,
 }
 
 // -------------------------------------------------------------- gemm --
+// gemm_prec of the linear ops: 0 = native (the tensor's own dtype on
+// the f32/f64 MFMA), 1 = bf16 operands with fp32 accumulation on the
+// bf16 MFMA (gemm_bf16.hip). This is the only place the bf16 choice is
+// written: it holds for fp32 tensors where the layer shape meets the
+// op's MFMA threshold (mfma_shape: use_mfma in linear_fwd /
+// linear_bwd_dx, Direct or Mfma from dw_kernel_for in linear_bwd_dw);
+// every other shape takes the kernel it takes natively.
+inline bool use_bf16_gemm(long gemm_prec, const torch::Tensor& t,
+                          bool mfma_shape) {
+  TORCH_CHECK(gemm_prec == 0 || gemm_prec == 1,
+              "gemm_prec must be 0 (native) or 1 (bf16)");
+  TORCH_CHECK(gemm_prec == 0 || t.scalar_type() == torch::kFloat,
+              "gemm_prec = 1 (bf16 operands) needs fp32 tensors");
+  return gemm_prec == 1 && mfma_shape;
+}
+
 void linear_fwd(torch::Tensor X, torch::Tensor theta, torch::Tensor Y,
                 c10::optional<torch::Tensor> Z, long w_off, long b_off,
-                long M, long I, long O, long act, double scale) {
+                long M, long I, long O, long act, double scale,
+                long gemm_prec = 0) {
   CHECK_DEV(X); CHECK_DEV(theta); CHECK_DEV(Y);
   const long L = theta.size(0), n = theta.size(1);
   // MFMA pays only when M fills the 64-row tiles across the chip;
   // small-M layers (MNIST fc, per-node B=64) stay on the VALU kernels.
   // I must be even for the 16-byte staging loads (vec2 alignment).
   const bool use_mfma = (M >= 128 && O >= 16 && I >= 8 && I % 2 == 0);
+  if (use_bf16_gemm(gemm_prec, X, use_mfma)) {
+    dim3 grid((O + 63) / 64, (M + 63) / 64, L);
+    hipLaunchKernelGGL(gbf16::bf16_fwd_k, grid, dim3(256), 0,
+        cur_stream(), X.data_ptr<float>(), theta.data_ptr<float>(),
+        Y.data_ptr<float>(), opt_ptr<float>(Z), n, w_off, b_off,
+        (int)M, (int)I, (int)O, (int)act, (float)scale);
+    HIP_CHECK_LAST();
+    return;
+  }
   DISPATCH_FT(X, {
     auto zp = opt_ptr<scalar_t>(Z);
     if (use_mfma) {
@@ -374,19 +401,29 @@ void linear_bwd_dx(torch::Tensor dZ, torch::Tensor theta,
                    long act_below, double scale_below,
                    long w_off, long M, long I, long O,
                    c10::optional<torch::Tensor> Xb2,
-                   long wb_off, long bb_off, long Ib) {
+                   long wb_off, long bb_off, long Ib,
+                   long gemm_prec = 0) {
   CHECK_DEV(dZ); CHECK_DEV(dX);
   const long L = theta.size(0), n = theta.size(1);
   const bool use_mfma =
       (M >= 128 && I >= 16 && O >= 8 && I % 2 == 0 && O % 2 == 0);
+  TORCH_CHECK(act_below == 0 || Yb.has_value(), "act_below needs Yb");
+  TORCH_CHECK(!Xb2.has_value() || Ib <= 4,
+              "z-recompute supports below-layer in_dim <= 4");
+  if (use_bf16_gemm(gemm_prec, dZ, use_mfma)) {
+    dim3 grid((I + 63) / 64, (M + 63) / 64, L);
+    hipLaunchKernelGGL(gbf16::bf16_dx_k, grid, dim3(256), 0,
+        cur_stream(), dZ.data_ptr<float>(), theta.data_ptr<float>(),
+        dX.data_ptr<float>(), opt_ptr<float>(Yb), opt_ptr<float>(Zb),
+        (int)act_below, (float)scale_below, n, w_off, (int)M, (int)I,
+        (int)O, opt_ptr<float>(Xb2), wb_off, bb_off, (int)Ib);
+    HIP_CHECK_LAST();
+    return;
+  }
   DISPATCH_FT(dZ, {
     auto ybp = opt_ptr<scalar_t>(Yb);
     auto zbp = opt_ptr<scalar_t>(Zb);
     auto xb2p = opt_ptr<scalar_t>(Xb2);
-    TORCH_CHECK(act_below == 0 || ybp != nullptr,
-                "act_below needs Yb");
-    TORCH_CHECK(xb2p == nullptr || Ib <= 4,
-                "z-recompute supports below-layer in_dim <= 4");
     static const bool dx_new = []() {
       const char* e = getenv("NDTA_DX_NEW");
       return !(e && e[0] == '0');
@@ -439,18 +476,61 @@ inline DwKernel dw_kernel_for(long M, long I, long O) {
 
 // true where linear_bwd_dw ADDS into gstack, so the layer's slice must
 // be zero on entry; the Small 16x16-tile store-path kernel overwrites
-bool dw_accumulates(long M, long I, long O) {
+inline bool dw_mfma_shape(long M, long I, long O) {
+  const DwKernel k = dw_kernel_for(M, I, O);
+  return k == DwKernel::Direct || k == DwKernel::Mfma;
+}
+
+bool dw_accumulates(long M, long I, long O, long gemm_prec = 0) {
+  // bf16_dw_k writes slabs that dw_reduce_parts_k folds with plain
+  // stores, db included: that path overwrites
+  if (gemm_prec == 1 && dw_mfma_shape(M, I, O)) return false;
   return dw_kernel_for(M, I, O) != DwKernel::Small;
 }
 
-// dW/db. PRECONDITION where dw_accumulates(M, I, O): the layer's slice
-// of gstack is zeroed (the stacked engine zeroes the whole grad stack
-// at backward start).
+// dW/db. PRECONDITION where dw_accumulates(M, I, O, gemm_prec): the
+// layer's slice of gstack is zeroed (the stacked engine zeroes the
+// whole grad stack at backward start).
 void linear_bwd_dw(torch::Tensor dZ, torch::Tensor X,
                    torch::Tensor gstack, long w_off, long b_off,
-                   long M, long I, long O) {
+                   long M, long I, long O, long gemm_prec = 0) {
   CHECK_DEV(dZ); CHECK_DEV(X); CHECK_DEV(gstack);
   const long L = gstack.size(0), n = gstack.size(1);
+  if (use_bf16_gemm(gemm_prec, dZ, dw_mfma_shape(M, I, O))) {
+    // M chunks of whole 64-row stages, about 1024 blocks in all; the
+    // last chunk alone is ragged and none is empty, so every slab
+    // element is written
+    const long tiles = ((I + 63) / 64) * ((O + 63) / 64);
+    long nchunk = std::max<long>(1, 1024 / std::max<long>(1, tiles * L));
+    nchunk = std::min<long>(nchunk, (M + 63) / 64);
+    const long mc = ((M + nchunk - 1) / nchunk + 63) / 64 * 64;
+    nchunk = (M + mc - 1) / mc;
+    torch::Tensor parts =
+        torch::empty({L * nchunk * (O * I + O)}, gstack.options());
+    // bias right behind the weights (every ModelSpec layer): chunk
+    // slabs are [dW | db] and one reduce launch folds both; any other
+    // layout keeps two slab arrays and two launches
+    const bool joint = b_off == w_off + O * I;
+    float* pp = parts.data_ptr<float>();
+    float* dbp = joint ? pp + O * I : pp + L * nchunk * O * I;
+    const long pstride = joint ? O * I + O : O * I;
+    const long dbstride = joint ? O * I + O : O;
+    dim3 grid((I + 63) / 64, (O + 63) / 64, L * nchunk);
+    hipLaunchKernelGGL(gbf16::bf16_dw_k, grid, dim3(256), 0,
+        cur_stream(), dZ.data_ptr<float>(), X.data_ptr<float>(), pp,
+        dbp, pstride, dbstride, (int)M, (int)I, (int)O, (int)mc,
+        (int)nchunk);
+    hipLaunchKernelGGL(gmfma::dw_reduce_parts_k<float>,
+        dim3(grid_1d(pstride), 1, L), dim3(256), 0, cur_stream(),
+        pp, gstack.data_ptr<float>(), n, w_off, pstride, (int)nchunk);
+    if (!joint) {
+      hipLaunchKernelGGL(gmfma::dw_reduce_parts_k<float>,
+          dim3(grid_1d(O), 1, L), dim3(256), 0, cur_stream(),
+          dbp, gstack.data_ptr<float>(), n, b_off, O, (int)nchunk);
+    }
+    HIP_CHECK_LAST();
+    return;
+  }
   DISPATCH_FT(dZ, {
     switch (dw_kernel_for(M, I, O)) {
     case DwKernel::Direct: {
@@ -1802,7 +1882,7 @@ void fwd_chain(torch::Tensor spec, torch::Tensor scales,
                std::vector<c10::optional<torch::Tensor>> zs,
                std::vector<c10::optional<torch::Tensor>> idxs,
                c10::optional<torch::Tensor> logp, long M,
-               bool train_skip_logp) {
+               bool train_skip_logp, long gemm_prec = 0) {
   TORCH_CHECK(spec.device().is_cpu() && scales.device().is_cpu() &&
                   spec.size(1) == SP_NCOLS,
               "spec [nl, 7] / scales must be CPU tensors");
@@ -1825,7 +1905,7 @@ void fwd_chain(torch::Tensor spec, torch::Tensor scales,
       cur = out;
     } else if (act == ACT_LOGSOFTMAX) {
       linear_fwd(cur, theta, out, c10::nullopt, w_off, b_off, M,
-                 in_dim, out_dim, ACT_NONE, 1.0);
+                 in_dim, out_dim, ACT_NONE, 1.0, gemm_prec);
       if (!train_skip_logp) {
         logsoftmax(out, *logp, out_dim);
         cur = *logp;
@@ -1834,7 +1914,7 @@ void fwd_chain(torch::Tensor spec, torch::Tensor scales,
       }
     } else {
       linear_fwd(cur, theta, out, zs[li], w_off, b_off, M, in_dim,
-                 out_dim, act, sc[li]);
+                 out_dim, act, sc[li], gemm_prec);
       cur = out;
     }
   }
@@ -1858,7 +1938,7 @@ void bwd_chain(torch::Tensor spec, torch::Tensor scales,
                long idx_stride, long idx_off,
                c10::optional<torch::Tensor> yb,
                c10::optional<torch::Tensor> loss, double loss_scale,
-               long M, long zero_mode) {
+               long M, long zero_mode, long gemm_prec = 0) {
   TORCH_CHECK(spec.device().is_cpu() && scales.device().is_cpu() &&
                   spec.size(1) == SP_NCOLS,
               "spec [nl, 7] / scales must be CPU tensors");
@@ -1907,7 +1987,8 @@ void bwd_chain(torch::Tensor spec, torch::Tensor scales,
                     out_dim, sp[li][SP_KSIZE], in_dim);
       continue;  // conv is the first layer: no dX
     }
-    linear_bwd_dw(dz, below, grad, w_off, b_off, M, in_dim, out_dim);
+    linear_bwd_dw(dz, below, grad, w_off, b_off, M, in_dim, out_dim,
+                  gemm_prec);
     if (li > 0) {
       const long act_b_raw = sp[li - 1][SP_ACT];
       const long act_b =
@@ -1926,7 +2007,7 @@ void bwd_chain(torch::Tensor spec, torch::Tensor scales,
           act_b ? c10::optional<torch::Tensor>(acts[li - 1])
                 : c10::nullopt,
           zs[li - 1], act_b, sc[li - 1], w_off, M, in_dim, out_dim,
-          xb2, wb_off, bb_off, ib);
+          xb2, wb_off, bb_off, ib, gemm_prec);
     }
   }
 }
@@ -1964,11 +2045,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("dinno_dual_threg_sched", &dinno_dual_threg_sched);
   mod.def("fused_step_sched", &fused_step_sched);
   mod.def("gather_targets", &gather_targets);
-  mod.def("linear_fwd", &linear_fwd);
+  namespace py = pybind11;
+  // gemm_prec trails with a default (0 = native, 1 = bf16 operands),
+  // so the positional calls from before it existed keep working
+  mod.def("linear_fwd", &linear_fwd, py::arg("X"), py::arg("theta"),
+          py::arg("Y"), py::arg("Z"), py::arg("w_off"), py::arg("b_off"),
+          py::arg("M"), py::arg("I"), py::arg("O"), py::arg("act"),
+          py::arg("scale"), py::arg("gemm_prec") = 0);
   mod.def("act_grad", &act_grad);
-  mod.def("linear_bwd_dx", &linear_bwd_dx);
-  mod.def("linear_bwd_dw", &linear_bwd_dw);
-  mod.def("dw_accumulates", &dw_accumulates);
+  mod.def("linear_bwd_dx", &linear_bwd_dx, py::arg("dZ"),
+          py::arg("theta"), py::arg("dX"), py::arg("Yb"), py::arg("Zb"),
+          py::arg("act_below"), py::arg("scale_below"), py::arg("w_off"),
+          py::arg("M"), py::arg("I"), py::arg("O"), py::arg("Xb2"),
+          py::arg("wb_off"), py::arg("bb_off"), py::arg("Ib"),
+          py::arg("gemm_prec") = 0);
+  mod.def("linear_bwd_dw", &linear_bwd_dw, py::arg("dZ"), py::arg("X"),
+          py::arg("gstack"), py::arg("w_off"), py::arg("b_off"),
+          py::arg("M"), py::arg("I"), py::arg("O"),
+          py::arg("gemm_prec") = 0);
+  mod.def("dw_accumulates", &dw_accumulates, py::arg("M"), py::arg("I"),
+          py::arg("O"), py::arg("gemm_prec") = 0);
   mod.def("conv_pool_fwd", &conv_pool_fwd);
   mod.def("conv_pool_bwd", &conv_pool_bwd);
   mod.def("conv_pool_fwd_idx", &conv_pool_fwd_idx);
@@ -1982,7 +2078,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ppo_loss_bwd", &ppo_loss_bwd);
   // the trailing optional outputs/inputs default to None, so the
   // positional calls from before they existed keep working
-  namespace py = pybind11;
   mod.def("ppo_rollout", &ppo_rollout, py::arg("theta"),
           py::arg("in_dims"), py::arg("out_dims"), py::arg("w_offs"),
           py::arg("b_offs"), py::arg("act_ids"), py::arg("resets"),
@@ -2010,6 +2105,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
 #ifdef NDTA_FC_PHASE_CLOCK
   mod.def("fc_phase_clock", &fc_phase_clock);
 #endif
-  mod.def("fwd_chain", &fwd_chain);
-  mod.def("bwd_chain", &bwd_chain);
+  mod.def("fwd_chain", &fwd_chain, py::arg("spec"), py::arg("scales"),
+          py::arg("X_all"), py::arg("idx"), py::arg("idx_stride"),
+          py::arg("idx_off"), py::arg("xb"), py::arg("theta"),
+          py::arg("acts"), py::arg("zs"), py::arg("idxs"),
+          py::arg("logp"), py::arg("M"), py::arg("train_skip_logp"),
+          py::arg("gemm_prec") = 0);
+  mod.def("bwd_chain", &bwd_chain, py::arg("spec"), py::arg("scales"),
+          py::arg("xb"), py::arg("theta"), py::arg("grad"),
+          py::arg("acts"), py::arg("zs"), py::arg("dzs"),
+          py::arg("idxs"), py::arg("loss_kind"), py::arg("Y_all"),
+          py::arg("idx"), py::arg("graph_offs"), py::arg("pit"),
+          py::arg("idx_stride"), py::arg("idx_off"), py::arg("yb"),
+          py::arg("loss"), py::arg("loss_scale"), py::arg("M"),
+          py::arg("zero_mode"), py::arg("gemm_prec") = 0);
 }

@@ -352,6 +352,30 @@ class PrimalStep:
         )
 
 
+def resolve_gemm_precision(conf, dtype, env=None) -> int:
+    """The ``gemm_prec`` the linear kernels get (0 native, 1 bf16
+    operands with fp32 accumulation) from the problem config's
+    ``gemm_precision`` key: "native" (default) or "bf16", which needs
+    ``precision: fp32``. Where the config does not set the key,
+    ``NDTA_GEMM_BF16=1`` in ``env`` turns the mode on for fp32 and is
+    ignored for fp64."""
+    env = os.environ if env is None else env
+    if "gemm_precision" not in conf:
+        on = env.get("NDTA_GEMM_BF16", "0") == "1"
+        return 1 if on and dtype == torch.float32 else 0
+    mode = conf["gemm_precision"]
+    if mode not in ("native", "bf16"):
+        raise ValueError(
+            f"gemm_precision must be 'native' or 'bf16', got {mode!r}"
+        )
+    if mode == "bf16" and dtype != torch.float32:
+        raise ValueError(
+            "gemm_precision: bf16 rounds fp32 operands on their way to "
+            "the matrix cores and needs precision: fp32"
+        )
+    return 1 if mode == "bf16" else 0
+
+
 class StackedEngine:
     def __init__(self, problem):
         self.ext = get_ext()
@@ -362,6 +386,9 @@ class StackedEngine:
             raise ValueError(
                 "stacked engine supports fp32/fp64 (precision knob)"
             )
+        # operand precision of the MFMA-shaped linear layers; the stack,
+        # gradients and every other kernel keep self.dtype
+        self.gemm_prec = resolve_gemm_precision(problem.conf, self.dtype)
 
         self.local_nodes = problem.local_nodes
         self.L = len(self.local_nodes)
@@ -624,7 +651,7 @@ class StackedEngine:
             ext.fwd_chain(
                 spec_t, scales_t, None, None, 0, 0, xb, self.theta,
                 bufs["acts"], bufs["zs"], bufs["idxs"], bufs["logp"],
-                M, train_skip_logp,
+                M, train_skip_logp, self.gemm_prec,
             )
             last = self.spec.layers[-1]
             if last.activation == "logsoftmax" and not train_skip_logp:
@@ -644,7 +671,7 @@ class StackedEngine:
                     ext.linear_fwd(
                         cur, self.theta, out, None, layer.w_off,
                         layer.b_off, M, layer.in_dim, layer.out_dim,
-                        ACT_IDS["none"], 1.0,
+                        ACT_IDS["none"], 1.0, self.gemm_prec,
                     )
                     # training backward consumes the LOGITS through the
                     # fused NLL kernel; log-probs are only materialized
@@ -656,6 +683,7 @@ class StackedEngine:
                         cur, self.theta, out, bufs["zs"][li],
                         layer.w_off, layer.b_off, M, layer.in_dim,
                         layer.out_dim, ACT_IDS[act], layer.scale,
+                        self.gemm_prec,
                     )
             # under train_skip_logp the logp buffer was never written —
             # hand back the logits (the training path consumes those
@@ -806,7 +834,8 @@ class StackedEngine:
                     cnt = (layer.out_dim * layer.kernel_size**2
                            + layer.out_dim)
                     slices.append((layer.w_off, cnt))
-                elif ext.dw_accumulates(M, layer.in_dim, layer.out_dim):
+                elif ext.dw_accumulates(M, layer.in_dim, layer.out_dim,
+                                        self.gemm_prec):
                     whole = True
             self._zero_plan = ("whole",) if whole else ("slices", slices)
         if self._use_chain:
@@ -834,7 +863,7 @@ class StackedEngine:
                 bufs["acts"], bufs["zs"], bufs["dzs"], bufs["idxs"],
                 loss_kind, self.Y_all if self.classification else None,
                 idx_t, graph_offs, pit, stride, idx_off, yb_arg,
-                loss_buf, loss_scale, M, zero_mode,
+                loss_buf, loss_scale, M, zero_mode, self.gemm_prec,
             )
             return loss_buf if want_loss else None
 
@@ -890,7 +919,7 @@ class StackedEngine:
                 continue  # conv is the first layer: no dX
             ext.linear_bwd_dw(
                 dz, below, self.grad, layer.w_off, layer.b_off, M,
-                layer.in_dim, layer.out_dim,
+                layer.in_dim, layer.out_dim, self.gemm_prec,
             )
             if li > 0:
                 # dX with the below layer's activation bwd fused into
@@ -918,7 +947,7 @@ class StackedEngine:
                     bufs["acts"][li - 1] if act_b else None,
                     bufs["zs"][li - 1], act_b, lb.scale,
                     layer.w_off, M, layer.in_dim, layer.out_dim,
-                    xb2, wb_off, bb_off, ib,
+                    xb2, wb_off, bb_off, ib, self.gemm_prec,
                 )
         return bufs["loss"] if want_loss else None
 

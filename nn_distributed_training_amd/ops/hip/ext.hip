@@ -8,6 +8,7 @@
 #include "gemm.hip"
 #include "gemm_mfma.hip"
 #include "gemm_bf16.hip"
+#include "mlp_fused.hip"
 #include "conv.hip"
 #include "losses.hip"
 #include "rollout.hip"
@@ -1873,24 +1874,188 @@ enum SpecCol {
   SP_NCOLS
 };
 
+// ---- whole-MLP forward in one launch (mlp_fused.hip) ------------------
+// mlp_plan is the one place that decides whether a chain is fusable
+// and lays out the block's LDS; mlp_fwd_fusable answers from it and
+// mlp_fwd_fused launches from it. A chain that is not fusable is no
+// error: fwd_chain then runs its layered loop.
+struct MlpPlan {
+  bool ok = false;
+  mlpf::Prog prog = {};
+  long lds = 0;
+};
+
+inline bool mlp_act_ok(long act, bool lift) {
+  return act == ACT_NONE || act == ACT_RELU || act == ACT_SIGMOID ||
+         act == ACT_TANH || (lift && act == ACT_SIN_RELU);
+}
+
+MlpPlan mlp_plan(const torch::Tensor& spec, long M, long gemm_prec,
+                 at::ScalarType dtype) {
+  TORCH_CHECK(spec.device().is_cpu() && spec.dim() == 2 &&
+                  spec.size(1) == SP_NCOLS &&
+                  spec.scalar_type() == torch::kLong,
+              "spec must be a CPU int64 [nl, 7] tensor");
+  MlpPlan pl;
+  const auto sp = spec.accessor<long, 2>();
+  const long nl = spec.size(0);
+  if (gemm_prec != 1 || dtype != torch::kFloat || M < 128 ||
+      M > (1L << 30) || nl < 2 || nl > mlpf::MAXL) {
+    return pl;
+  }
+  const bool has_tail =
+      nl >= 3 && sp[nl - 1][SP_OUT_DIM] <= mlpf::TAIL_OUT;
+  auto r32 = [](long v) { return (v + 31) / 32 * 32; };
+  long img = 0, par = 0;  // bytes of weight images, floats of fp32 params
+  for (long li = 0; li < nl; ++li) {
+    const long in = sp[li][SP_IN_DIM], out = sp[li][SP_OUT_DIM],
+               act = sp[li][SP_ACT];
+    if (sp[li][SP_KIND] != 0 || in < 1 || out < 1) return pl;
+    if (li > 0 && in != sp[li - 1][SP_OUT_DIM]) return pl;
+    if (!mlp_act_ok(act, li == 0)) return pl;  // no Z stash, no logsoftmax
+    mlpf::Layer& y = pl.prog.ly[li];
+    y.w_off = sp[li][SP_W_OFF];
+    y.b_off = sp[li][SP_B_OFF];
+    y.in = (int)in;
+    y.out = (int)out;
+    y.act = (int)act;
+    y.scale = 1.f;
+    y.img = 0;
+    y.par = (int)par;
+    y.vec = 0;
+    if (li == 0) {
+      if (in > mlpf::LIFT_IN || out > mlpf::LIFT_OUT) return pl;
+      par += r32(out) * 5;
+    } else if (has_tail && li == nl - 1) {
+      par += mlpf::TAIL_OUT * 64 + mlpf::TAIL_OUT;  // in <= 64: chain
+    } else {
+      if (in > mlpf::TRUNK_IN || out > mlpf::TRUNK_OUT) return pl;
+      y.img = (int)img;
+      img += mlpf::TRUNK_OUT * (r32(in) + 8) * 2;
+      par += mlpf::TRUNK_OUT;
+    }
+  }
+  mlpf::Prog& pg = pl.prog;
+  pg.nl = (int)nl;
+  pg.has_tail = has_tail ? 1 : 0;
+  pg.off_wide = (int)img;
+  pg.off_narrow = pg.off_wide + mlpf::TM * mlpf::LDW * 2;
+  pg.off_tail = pg.off_narrow + mlpf::TM * mlpf::LDN * 2;
+  pg.off_par = pg.off_tail + (has_tail ? mlpf::TM * mlpf::LDT * 4 : 0);
+  pl.lds = pg.off_par + par * 4;
+  pl.ok = pl.lds <= mlpf::LDS_BUDGET;
+  return pl;
+}
+
+bool mlp_fwd_fusable(torch::Tensor spec, long M, long gemm_prec,
+                     at::ScalarType dtype) {
+  return mlp_plan(spec, M, gemm_prec, dtype).ok;
+}
+
+// acts: one entry per layer, [L*M, out] fp32. All present = the
+// training forward (every layer stashed for bwd_chain); only the last
+// present = inference. max_blocks > 0 caps the persistent grid.
+void mlp_fwd_fused(torch::Tensor spec, torch::Tensor scales,
+                   torch::Tensor xb, torch::Tensor theta,
+                   std::vector<c10::optional<torch::Tensor>> acts, long M,
+                   long max_blocks = 0) {
+  CHECK_DEV(xb); CHECK_DEV(theta);
+  TORCH_CHECK(theta.dim() == 2 && theta.is_contiguous() &&
+                  xb.is_contiguous(),
+              "mlp_fwd_fused: theta [L, n] and xb must be contiguous");
+  MlpPlan pl = mlp_plan(spec, M, 1, theta.scalar_type());
+  TORCH_CHECK(pl.ok && xb.scalar_type() == torch::kFloat,
+              "mlp_fwd_fused: this chain is not fusable "
+              "(mlp_fwd_fusable decides)");
+  mlpf::Prog& pg = pl.prog;
+  const long nl = pg.nl, L = theta.size(0), n = theta.size(1);
+  TORCH_CHECK(scales.device().is_cpu() && scales.numel() == nl &&
+                  scales.scalar_type() == torch::kDouble &&
+                  (long)acts.size() == nl,
+              "mlp_fwd_fused: scales / acts need one entry per layer");
+  TORCH_CHECK(max_blocks >= 0 && L >= 1 &&
+                  xb.numel() == L * M * pg.ly[0].in,
+              "mlp_fwd_fused: xb must be [L*M, in_dim]");
+  TORCH_CHECK(acts[nl - 1].has_value(),
+              "mlp_fwd_fused: the last acts entry is the output");
+  long present = 0;
+  for (long li = 0; li < nl; ++li) present += acts[li].has_value();
+  TORCH_CHECK(present == nl || present == 1,
+              "mlp_fwd_fused: give every layer's buffer or the last only");
+  const auto sc = scales.accessor<double, 1>();
+  for (long li = 0; li < nl; ++li) {
+    mlpf::Layer& y = pg.ly[li];
+    y.scale = (float)sc[li];
+    TORCH_CHECK(y.w_off >= 0 && y.b_off >= 0 &&
+                    y.w_off + (long)y.in * y.out <= n &&
+                    y.b_off + y.out <= n,
+                "mlp_fwd_fused: layer ", li, " lies outside the stack");
+    pg.stash[li] = nullptr;
+    if (!acts[li].has_value()) continue;
+    const torch::Tensor& a = *acts[li];
+    CHECK_DEV(a);
+    TORCH_CHECK(a.scalar_type() == torch::kFloat && a.is_contiguous() &&
+                    a.numel() == L * M * y.out,
+                "mlp_fwd_fused: acts[", li, "] must be fp32 [L*M, out]");
+    pg.stash[li] = a.data_ptr<float>();
+    y.vec = (y.out % 4 == 0 &&
+             reinterpret_cast<uintptr_t>(pg.stash[li]) % 16 == 0) ? 1 : 0;
+  }
+  const long total = L * ((M + mlpf::TM - 1) / mlpf::TM);
+  const long cap = max_blocks > 0
+      ? max_blocks
+      : at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  const dim3 grid((unsigned)std::min(total, cap));
+  auto launch = [&](auto stash_tag) {
+    constexpr bool STASH = decltype(stash_tag)::value;
+    static bool lds_raised = false;  // once per variant: > 64 KB of LDS
+    if (!lds_raised) {
+      TORCH_CHECK(hipFuncSetAttribute(
+                      reinterpret_cast<const void*>(
+                          mlpf::mlp_fwd_fused_k<STASH>),
+                      hipFuncAttributeMaxDynamicSharedMemorySize,
+                      (int)mlpf::LDS_BUDGET) == hipSuccess,
+                  "mlp_fwd_fused: cannot raise the dynamic LDS limit");
+      lds_raised = true;
+    }
+    hipLaunchKernelGGL(mlpf::mlp_fwd_fused_k<STASH>, grid, dim3(256),
+        (size_t)pl.lds, cur_stream(), xb.data_ptr<float>(),
+        theta.data_ptr<float>(), pg, n, (int)M, (int)L);
+  };
+  if (present == nl) launch(std::true_type{});
+  else launch(std::false_type{});
+  HIP_CHECK_LAST();
+}
+
+// fuse (trailing, default 0): 1 = run a chain that mlp_fwd_fusable
+// accepts as the optional gather plus ONE mlp_fwd_fused launch; any
+// other chain, and fuse = 0, run the layered loop below unchanged. An
+// acts entry may be None only for a layer the fused launch does not
+// stash.
 void fwd_chain(torch::Tensor spec, torch::Tensor scales,
                c10::optional<torch::Tensor> X_all,
                c10::optional<torch::Tensor> idx, long idx_stride,
                long idx_off,
                torch::Tensor xb, torch::Tensor theta,
-               std::vector<torch::Tensor> acts,
+               std::vector<c10::optional<torch::Tensor>> acts,
                std::vector<c10::optional<torch::Tensor>> zs,
                std::vector<c10::optional<torch::Tensor>> idxs,
                c10::optional<torch::Tensor> logp, long M,
-               bool train_skip_logp, long gemm_prec = 0) {
+               bool train_skip_logp, long gemm_prec = 0, long fuse = 0) {
   TORCH_CHECK(spec.device().is_cpu() && scales.device().is_cpu() &&
                   spec.size(1) == SP_NCOLS,
               "spec [nl, 7] / scales must be CPU tensors");
+  TORCH_CHECK(fuse == 0 || fuse == 1, "fuse must be 0 or 1");
   const auto sp = spec.accessor<long, 2>();
   const auto sc = scales.accessor<double, 1>();
   const long nl = spec.size(0);
   if (X_all.has_value()) {
     gather_batch(*X_all, *idx, xb, idx_stride, idx_off);
+  }
+  if (fuse == 1 &&
+      mlp_fwd_fusable(spec, M, gemm_prec, theta.scalar_type())) {
+    mlp_fwd_fused(spec, scales, xb, theta, acts, M);
+    return;
   }
   torch::Tensor cur = xb;
   for (long li = 0; li < nl; ++li) {
@@ -1898,7 +2063,9 @@ void fwd_chain(torch::Tensor spec, torch::Tensor scales,
                b_off = sp[li][SP_B_OFF], in_dim = sp[li][SP_IN_DIM],
                out_dim = sp[li][SP_OUT_DIM], act = sp[li][SP_ACT],
                ksize = sp[li][SP_KSIZE];
-    torch::Tensor out = acts[li];
+    TORCH_CHECK(acts[li].has_value(),
+                "fwd_chain: the layered path needs every acts buffer");
+    torch::Tensor out = *acts[li];
     if (kind == 1) {
       conv_pool_fwd(cur, theta, out, *idxs[li], w_off, b_off, M,
                     out_dim, ksize, in_dim);
@@ -2110,7 +2277,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("idx_off"), py::arg("xb"), py::arg("theta"),
           py::arg("acts"), py::arg("zs"), py::arg("idxs"),
           py::arg("logp"), py::arg("M"), py::arg("train_skip_logp"),
-          py::arg("gemm_prec") = 0);
+          py::arg("gemm_prec") = 0, py::arg("fuse") = 0);
+  mod.def("mlp_fwd_fusable", &mlp_fwd_fusable, py::arg("spec"),
+          py::arg("M"), py::arg("gemm_prec"), py::arg("dtype"));
+  mod.def("mlp_fwd_fused", &mlp_fwd_fused, py::arg("spec"),
+          py::arg("scales"), py::arg("xb"), py::arg("theta"),
+          py::arg("acts"), py::arg("M"), py::arg("max_blocks") = 0);
   mod.def("bwd_chain", &bwd_chain, py::arg("spec"), py::arg("scales"),
           py::arg("xb"), py::arg("theta"), py::arg("grad"),
           py::arg("acts"), py::arg("zs"), py::arg("dzs"),

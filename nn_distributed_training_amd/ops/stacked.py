@@ -376,6 +376,31 @@ def resolve_gemm_precision(conf, dtype, env=None) -> int:
     return 1 if mode == "bf16" else 0
 
 
+def resolve_fused_forward(conf, dtype, gemm_prec, env=None) -> bool:
+    """Whether the forward chain asks for the one-launch whole-MLP
+    kernel (ops/hip/mlp_fused.hip), from the problem config's
+    ``fused_forward`` key: false (default) or true, which needs the bf16
+    operands of ``gemm_precision: bf16``. Where the config does not set
+    the key, ``NDTA_FUSED_FWD=1`` in ``env`` turns it on under bf16
+    operands and is ignored otherwise. A chain the kernel cannot take
+    (ext.mlp_fwd_fusable) runs layered whatever the flag."""
+    env = os.environ if env is None else env
+    bf16 = gemm_prec == 1 and dtype == torch.float32
+    if "fused_forward" not in conf:
+        return bf16 and env.get("NDTA_FUSED_FWD", "0") == "1"
+    on = conf["fused_forward"]
+    if not isinstance(on, bool):
+        raise ValueError(
+            f"fused_forward must be true or false, got {on!r}"
+        )
+    if on and not bf16:
+        raise ValueError(
+            "fused_forward: true runs the linear layers on bf16 operands "
+            "and needs gemm_precision: bf16"
+        )
+    return on
+
+
 class StackedEngine:
     def __init__(self, problem):
         self.ext = get_ext()
@@ -389,6 +414,10 @@ class StackedEngine:
         # operand precision of the MFMA-shaped linear layers; the stack,
         # gradients and every other kernel keep self.dtype
         self.gemm_prec = resolve_gemm_precision(problem.conf, self.dtype)
+        # one-launch forward of the C++ chain where the chain is fusable
+        self.fused_fwd = resolve_fused_forward(
+            problem.conf, self.dtype, self.gemm_prec
+        )
 
         self.local_nodes = problem.local_nodes
         self.L = len(self.local_nodes)
@@ -503,8 +532,20 @@ class StackedEngine:
             L * M, el, device=self.device, dtype=self.dtype
         )
         acts, zs, dzs, idxs = [], [], [], []
+        # a validation pack of a fused forward keeps no intermediate
+        # activation: the kernel's inference variant writes the output
+        infer = (
+            not train and self.fused_fwd and self._use_chain
+            and self.ext.mlp_fwd_fusable(
+                self._chain_meta()[0], M, self.gemm_prec, self.dtype
+            )
+        )
+        last = self.spec.layers[-1]
         for layer in self.spec.layers:
-            acts.append(mk(layer.out_elems))
+            acts.append(
+                None if infer and layer is not last
+                else mk(layer.out_elems)
+            )
             # sin_relu needs z in backward, but for a tiny in_dim the
             # dx epilogue RECOMPUTES it (4 flops) instead of storing /
             # re-reading an [L*M, out] tensor (kernel z-recompute mode)
@@ -652,6 +693,7 @@ class StackedEngine:
                 spec_t, scales_t, None, None, 0, 0, xb, self.theta,
                 bufs["acts"], bufs["zs"], bufs["idxs"], bufs["logp"],
                 M, train_skip_logp, self.gemm_prec,
+                1 if self.fused_fwd else 0,
             )
             last = self.spec.layers[-1]
             if last.activation == "logsoftmax" and not train_skip_logp:

@@ -9,6 +9,7 @@
 // routes between them.
 
 #include "common.h"
+#include "linear_epilogue.h"
 
 namespace gemm {
 
@@ -144,7 +145,7 @@ __global__ void act_grad_k(
 
 // dX[M,I] = dZ[M,O] @ W[O,I], below-layer activation bwd fused
 // (Xb2 != null: recompute z_below from the below layer's tiny input
-// instead of reading Zb — see gemm_mfma.hip mfma_dx_k)
+// instead of reading Zb — EPI_BELOW_ACT_FACTOR, linear_epilogue.h)
 template <typename T>
 __global__ void linear_bwd_dx_k(
     const T* __restrict__ dZ, const T* __restrict__ theta,
@@ -182,21 +183,9 @@ __global__ void linear_bwd_dx_k(
   if (m < M && i < I) {
     const long off = l * (long)M * I + (long)m * I + i;
     if (act_below != ACT_NONE) {
-      T z = T(0);
-      if (Xb2 != nullptr) {
-        const T* Wb = theta + l * n + wb_off;
-        z = theta[l * n + bb_off + i];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (j < Ib) {
-            z += Xb2[(long)(l * (long)M + m) * Ib + j]
-                 * Wb[(long)i * Ib + j];
-          }
-        }
-      } else if (Zb != nullptr) {
-        z = Zb[off];
-      }
-      acc *= act_bwd(act_below, z, Yb ? Yb[off] : T(0), scale_below);
+      EPI_BELOW_ACT_FACTOR(T, acc, act_below, scale_below, Yb, Zb, off,
+                           Xb2, theta + l * n + wb_off,
+                           theta + l * n + bb_off, l, M, m, i, Ib);
     }
     dX[off] = acc;
   }

@@ -1,13 +1,15 @@
 // Mixed-precision stacked linear kernels (CDNA4 gfx950): fp32 storage,
 // bf16 MFMA operands, fp32 accumulation.
 //
-// Same [L, n] fp32 parameter stack, fp32 activation buffers, arguments
-// and epilogues as the float instantiations of gmfma::mfma_fwd_k /
+// Same [L, n] fp32 parameter stack, fp32 activation buffers and
+// arguments as the float instantiations of gmfma::mfma_fwd_k /
 // mfma_dx_k / mfma_dw_k; only the operands of the contraction are
 // rounded (RNE) to bf16 on their way to v_mfma_f32_16x16x32_bf16,
 // which contracts 8 k-values per lane per instruction where the
 // 16x16x4 f32 shape contracts one. Bias, activation, masks, db and
-// every result stay fp32.
+// every result stay fp32. The fwd and dx kernels end in the SAME
+// epilogues as the float kernels (EPI_FWD_EPILOGUE, EPI_DX_EPILOGUE
+// in linear_epilogue.h, with the f32 lane map).
 //
 // Geometry (all three kernels): 256-thread blocks = 4 waves in a 2x2
 // grid over a 64x64 output tile, each wave a 32x32 sub-tile as 2x2
@@ -22,6 +24,7 @@
 //   A operand: lane l holds A[l&15][8*(l>>4) .. +7]   (8 bf16, 16 B)
 //   B operand: lane l holds B[8*(l>>4) .. +7][l&15]
 //   C/D:       the f32 16x16 map, row (l>>4)*4 + r, col l&15
+//              (epi::acc_map<float>)
 // Both operands want 8 CONSECUTIVE k per lane, so both LDS images are
 // k-contiguous: As[row][k], Bs[col][k], and a fragment is one 16-byte
 // LDS read.
@@ -63,12 +66,13 @@
 // The kernels are compiled without packed fp32 VALU ops.
 
 #include "common.h"
+#include "linear_epilogue.h"
 
 namespace gbf16 {
 
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using epi::f32x4;
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define GBF16_KERNEL \
@@ -215,8 +219,6 @@ DEV_INLINE void mma_stage(const __bf16* As, const __bf16* Bs, int wm,
   }
 }
 
-DEV_INLINE int acc_row(int lane, int r) { return (lane >> 4) * 4 + r; }
-
 // ---------------------------------------------------------------------
 // NT: Y[M,O] = act(bf(X[M,I]) @ bf(W_l[O,I])^T + b_l)  [+ optional Z]
 GBF16_KERNEL __launch_bounds__(256) void bf16_fwd_k(
@@ -261,51 +263,15 @@ GBF16_KERNEL __launch_bounds__(256) void bf16_fwd_k(
   }
 
   const bool full_mo = (m0 + TM) <= M && (o0 + TN) <= O;
-  if (full_mo && Z == nullptr) {  // guard-free store chain
-    float bv[2];
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn) {
-      bv[fn] = bias[o0 + wn + fn * 16 + (lane & 15)];
-    }
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + wm + fm * 16 + acc_row(lane, r);
-          const int o = o0 + wn + fn * 16 + (lane & 15);
-          const long off = l * (long)M * O + (long)m * O + o;
-          Y[off] = act_fwd(act, acc[fm][fn][r] + bv[fn], scale);
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm + fm * 16 + acc_row(lane, r);
-        const int o = o0 + wn + fn * 16 + (lane & 15);
-        if (m < M && o < O) {
-          const float z = acc[fm][fn][r] + bias[o];
-          const long off = l * (long)M * O + (long)m * O + o;
-          if (Z != nullptr) Z[off] = z;
-          Y[off] = act_fwd(act, z, scale);
-        }
-      }
-    }
-  }
+  EPI_FWD_EPILOGUE(float, epi::acc_map<float>, acc, bias, Y, Z, l, M, O,
+                   m0, o0, wm, wn, lane, act, scale, full_mo);
 }
 
 // ---------------------------------------------------------------------
 // NN: dX[M,I] = bf(dZ[M,O]) @ bf(W_l[O,I])  (contraction over O), with
 // the BELOW layer's activation backward in the epilogue from the fp32
 // Yb / Zb, or from z recomputed out of the below layer's tiny input
-// (Xb2, Ib <= 4) exactly as mfma_dx_k does.
+// (Xb2, Ib <= 4): EPI_DX_EPILOGUE, shared with mfma_dx_k.
 GBF16_KERNEL __launch_bounds__(256) void bf16_dx_k(
     const float* __restrict__ dZ, const float* __restrict__ theta,
     float* __restrict__ dX,
@@ -350,109 +316,9 @@ GBF16_KERNEL __launch_bounds__(256) void bf16_dx_k(
   const bool full_mi = (m0 + TM) <= M && (i0 + TN) <= I;
   const float* Wb = theta + l * n + wb_off;
   const float* bb = theta + l * n + bb_off;
-  if (full_mi && act_below == ACT_RELU) {
-    // guard-free: all 16 mask loads issued before the stores
-    float yv[2][2][4];
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + wm + fm * 16 + acc_row(lane, r);
-          const int i = i0 + wn + fn * 16 + (lane & 15);
-          yv[fm][fn][r] = Yb[l * (long)M * I + (long)m * I + i];
-        }
-      }
-    }
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + wm + fm * 16 + acc_row(lane, r);
-          const int i = i0 + wn + fn * 16 + (lane & 15);
-          const long off = l * (long)M * I + (long)m * I + i;
-          dX[off] = yv[fm][fn][r] > 0.f ? acc[fm][fn][r] : 0.f;
-        }
-      }
-    }
-    return;
-  }
-  if (full_mi && act_below == ACT_SIN_RELU && Xb2 != nullptr
-      && Ib == 2) {
-    // encode-below: z from the 2-wide input, loads before the sin/cos
-    float x0v[2][4], x1v[2][4];
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm + fm * 16 + acc_row(lane, r);
-        const long xoff = (long)(l * (long)M + m) * 2;
-        x0v[fm][r] = Xb2[xoff];
-        x1v[fm][r] = Xb2[xoff + 1];
-      }
-    }
-    float w0v[2], w1v[2], bv[2];
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn) {
-      const int i = i0 + wn + fn * 16 + (lane & 15);
-      w0v[fn] = Wb[(long)i * 2];
-      w1v[fn] = Wb[(long)i * 2 + 1];
-      bv[fn] = bb[i];
-    }
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + wm + fm * 16 + acc_row(lane, r);
-          const int i = i0 + wn + fn * 16 + (lane & 15);
-          const long off = l * (long)M * I + (long)m * I + i;
-          const float z = bv[fn] + x0v[fm][r] * w0v[fn]
-                          + x1v[fm][r] * w1v[fn];
-          dX[off] = acc[fm][fn][r]
-                    * act_bwd(ACT_SIN_RELU, z, 0.f, scale_below);
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm + fm * 16 + acc_row(lane, r);
-        const int i = i0 + wn + fn * 16 + (lane & 15);
-        if (m < M && i < I) {
-          const long off = l * (long)M * I + (long)m * I + i;
-          float v = acc[fm][fn][r];
-          if (act_below != ACT_NONE) {
-            float z = 0.f;
-            if (Xb2 != nullptr) {  // recompute z_below (tiny Ib)
-              z = bb[i];
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                if (j < Ib) {
-                  z += Xb2[(long)(l * (long)M + m) * Ib + j]
-                       * Wb[(long)i * Ib + j];
-                }
-              }
-            } else if (Zb != nullptr) {
-              z = Zb[off];
-            }
-            v *= act_bwd(act_below, z, Yb ? Yb[off] : 0.f,
-                         scale_below);
-          }
-          dX[off] = v;
-        }
-      }
-    }
-  }
+  EPI_DX_EPILOGUE(float, epi::acc_map<float>, acc, dX, Yb, Zb, act_below,
+                  scale_below, Wb, bb, Xb2, Ib, l, M, I, m0, i0, wm, wn,
+                  lane, full_mi);
 }
 
 // ---------------------------------------------------------------------
@@ -532,7 +398,8 @@ GBF16_KERNEL __launch_bounds__(256) void bf16_dw_k(
     for (int fn = 0; fn < 2; ++fn) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int o = o0 + wm + fm * 16 + acc_row(lane, r);
+        const int o =
+            o0 + wm + fm * 16 + epi::acc_map<float>::acc_row(lane, r);
         const int i = i0 + wn + fn * 16 + (lane & 15);
         if (full_oi || (o < O && i < I)) {
           slab[(long)o * I + i] = acc[fm][fn][r];

@@ -14,6 +14,12 @@
 //   B operand: lane l holds B[k = l>>4][j = l&15]
 //   C/D:       4 elements, col l&15; row differs BY DTYPE:
 //              f32: (l>>4)*4 + r      f64: 4*r + (l>>4)
+//              (epi::acc_map in linear_epilogue.h)
+//
+// The fwd and dx epilogues (bias + activation + Z stash; below-layer
+// activation backward with its fast paths) are EPI_FWD_EPILOGUE and
+// EPI_DX_EPILOGUE of linear_epilogue.h, the one implementation that
+// gemm_bf16.hip's kernels end in as well.
 //
 // Three contraction variants cover fwd/bwd:
 //   NT (fwd):  Y[M,O] = act(X[M,I] @ W[O,I]^T + b)   contraction I
@@ -24,36 +30,29 @@
 //              256-CU chip instead of serializing in one block's K loop.
 
 #include "common.h"
+#include "linear_epilogue.h"
 
 namespace gmfma {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using epi::f32x4;
+using epi::f64x4;
 
+// the MFMA of element type T on top of its accumulator type and lane
+// map (acc_t, acc_row)
 template <typename T>
 struct mfma_t;
 
 template <>
-struct mfma_t<double> {
-  using acc_t = f64x4;
+struct mfma_t<double> : epi::acc_map<double> {
   static DEV_INLINE acc_t mma(double a, double b, acc_t c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  // measured on gfx950 (tools/mfma_probe.hip): f64 acc rows interleave
-  // as 4*reg + (lane>>4) — DIFFERENT from the f32 form
-  static DEV_INLINE int acc_row(int lane, int r) {
-    return 4 * r + (lane >> 4);
   }
 };
 
 template <>
-struct mfma_t<float> {
-  using acc_t = f32x4;
+struct mfma_t<float> : epi::acc_map<float> {
   static DEV_INLINE acc_t mma(float a, float b, acc_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static DEV_INLINE int acc_row(int lane, int r) {
-    return (lane >> 4) * 4 + r;
   }
 };
 
@@ -182,47 +181,8 @@ __global__ __launch_bounds__(256) void mfma_fwd_k(
     }
   }
 
-  // epilogue: bias + activation, coalesced per-fragment store.
-  // Full tiles store guard-free (per-element bounds guards serialize
-  // the store chain — trap 4c).
-  if (full_mo && Z == nullptr) {
-    T bv[2];
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn) {
-      bv[fn] = bias[o0 + wn + fn * 16 + (lane & 15)];
-    }
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + wm + fm * 16 + MF::acc_row(lane, r);
-          const int o = o0 + wn + fn * 16 + (lane & 15);
-          const long off = l * (long)M * O + (long)m * O + o;
-          Y[off] = act_fwd(act, acc[fm][fn][r] + bv[fn], scale);
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm + fm * 16 + MF::acc_row(lane, r);
-        const int o = o0 + wn + fn * 16 + (lane & 15);
-        if (m < M && o < O) {
-          const T z = acc[fm][fn][r] + bias[o];
-          const long off = l * (long)M * O + (long)m * O + o;
-          if (Z != nullptr) Z[off] = z;
-          Y[off] = act_fwd(act, z, scale);
-        }
-      }
-    }
-  }
+  EPI_FWD_EPILOGUE(T, MF, acc, bias, Y, Z, l, M, O, m0, o0, wm, wn, lane,
+                   act, scale, full_mo);
 }
 
 // ---------------------------------------------------------------------
@@ -232,12 +192,9 @@ __global__ __launch_bounds__(256) void mfma_fwd_k(
 // pass was ~14% of the density round.
 //
 // Round-2: same T14 write-after-barrier register pipeline + BK=32 +
-// vec2 staging as mfma_fwd_k, and an optional RECOMPUTE mode for the
-// below layer's pre-activation: when the below layer has a tiny input
-// (the FourierNet encode, Ib = 2), z_below is recomputed from
-// Xb2 @ W_below^T + b_below in the epilogue (4 flops + L1-resident
-// reads) instead of reading a full [M, I] Zb tensor back from HBM
-// (328 MB/call in the density config).
+// vec2 staging as mfma_fwd_k. The epilogue, with its optional
+// RECOMPUTE mode for the below layer's pre-activation (Xb2 != null),
+// is EPI_DX_EPILOGUE.
 template <typename T>
 __global__ __launch_bounds__(256) void mfma_dx_k(
     const T* __restrict__ dZ, const T* __restrict__ theta,
@@ -363,112 +320,8 @@ __global__ __launch_bounds__(256) void mfma_dx_k(
 
   const T* Wb = theta + l * n + wb_off;
   const T* bb = theta + l * n + bb_off;
-  if (full_mi && act_below == ACT_RELU) {
-    // guard-free fast path for the relu-below layers: prefetch the 16
-    // Yb mask values unconditionally, then compute + store (per-
-    // element bounds guards serialized this epilogue — trap 4c)
-    T yv[2][2][4];
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + wm + fm * 16 + MF::acc_row(lane, r);
-          const int i = i0 + wn + fn * 16 + (lane & 15);
-          yv[fm][fn][r] = Yb[l * (long)M * I + (long)m * I + i];
-        }
-      }
-    }
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + wm + fm * 16 + MF::acc_row(lane, r);
-          const int i = i0 + wn + fn * 16 + (lane & 15);
-          const long off = l * (long)M * I + (long)m * I + i;
-          dX[off] = yv[fm][fn][r] > T(0) ? acc[fm][fn][r] : T(0);
-        }
-      }
-    }
-    return;
-  }
-  if (full_mi && act_below == ACT_SIN_RELU && Xb2 != nullptr
-      && Ib == 2) {
-    // encode-below fast path: z recomputed from the 2-wide input,
-    // all loads issued before the sin/cos block
-    T x0v[2][4], x1v[2][4];
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm + fm * 16 + MF::acc_row(lane, r);
-        const long xoff = (long)(l * (long)M + m) * 2;
-        x0v[fm][r] = Xb2[xoff];
-        x1v[fm][r] = Xb2[xoff + 1];
-      }
-    }
-    T w0v[2], w1v[2], bv[2];
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn) {
-      const int i = i0 + wn + fn * 16 + (lane & 15);
-      w0v[fn] = Wb[(long)i * 2];
-      w1v[fn] = Wb[(long)i * 2 + 1];
-      bv[fn] = bb[i];
-    }
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-      for (int fn = 0; fn < 2; ++fn) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + wm + fm * 16 + MF::acc_row(lane, r);
-          const int i = i0 + wn + fn * 16 + (lane & 15);
-          const long off = l * (long)M * I + (long)m * I + i;
-          const T z = bv[fn] + x0v[fm][r] * w0v[fn]
-                      + x1v[fm][r] * w1v[fn];
-          dX[off] = acc[fm][fn][r]
-                    * act_bwd(ACT_SIN_RELU, z, T(0), scale_below);
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int fm = 0; fm < 2; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm + fm * 16 + MF::acc_row(lane, r);
-        const int i = i0 + wn + fn * 16 + (lane & 15);
-        if (m < M && i < I) {
-          const long off = l * (long)M * I + (long)m * I + i;
-          T v = acc[fm][fn][r];
-          if (act_below != ACT_NONE) {
-            T z = T(0);
-            if (Xb2 != nullptr) {  // recompute z_below (tiny Ib)
-              z = bb[i];
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                if (j < Ib) {
-                  z += Xb2[(long)(l * (long)M + m) * Ib + j]
-                       * Wb[(long)i * Ib + j];
-                }
-              }
-            } else if (Zb != nullptr) {
-              z = Zb[off];
-            }
-            v *= act_bwd(act_below, z, Yb ? Yb[off] : T(0),
-                         scale_below);
-          }
-          dX[off] = v;
-        }
-      }
-    }
-  }
+  EPI_DX_EPILOGUE(T, MF, acc, dX, Yb, Zb, act_below, scale_below, Wb, bb,
+                  Xb2, Ib, l, M, I, m0, i0, wm, wn, lane, full_mi);
 }
 
 // ---------------------------------------------------------------------
@@ -663,22 +516,9 @@ __global__ __launch_bounds__(256) void mfma_dx16_k(
           const long off = l * (long)M * I + (long)m * I + i;
           T v = acc[fm][fn][r];
           if (act_below != ACT_NONE) {
-            T z = T(0);
-            if (Xb2 != nullptr) {
-              const T* Wb = theta + l * n + wb_off;
-              z = theta[l * n + bb_off + i];
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                if (j < Ib) {
-                  z += Xb2[(long)(l * (long)M + m) * Ib + j]
-                       * Wb[(long)i * Ib + j];
-                }
-              }
-            } else if (Zb != nullptr) {
-              z = Zb[off];
-            }
-            v *= act_bwd(act_below, z, Yb ? Yb[off] : T(0),
-                         scale_below);
+            EPI_BELOW_ACT_FACTOR(T, v, act_below, scale_below, Yb, Zb,
+                                 off, Xb2, theta + l * n + wb_off,
+                                 theta + l * n + bb_off, l, M, m, i, Ib);
           }
           dX[off] = v;
         }

@@ -14,6 +14,7 @@
 #include "rollout.hip"
 #include "advantage.hip"
 #include "fused_mnist.hip"
+#include "ppo_fused.hip"
 
 #include <ATen/hip/HIPContext.h>
 
@@ -1060,6 +1061,237 @@ void ppo_rollout(torch::Tensor theta, std::vector<long> in_dims,
     };
     if (wlds) launch(std::true_type{});
     else launch(std::false_type{});
+  });
+  HIP_CHECK_LAST();
+}
+
+// ---- every node's PPO gradient row in one launch (ppo_fused.hip) ------
+// ppo_grads_plan is the one place that decides whether a pair of nets
+// is fusable and lays out the block's LDS; ppo_grads_fusable and
+// ppo_grads_limit (the violated limit in words, "" where there is none)
+// answer from it and ppo_grads_fused launches from it. The layer lists
+// are those of ppo_rollout: the actor's shifted_plan, then the critic's.
+struct PpoPlan {
+  std::string why;  // empty: fusable
+  ppof::Prog prog = {};
+  long lds = 0;     // dynamic LDS bytes
+};
+
+PpoPlan ppo_grads_plan(
+    const std::vector<long>& a_in, const std::vector<long>& a_out,
+    const std::vector<long>& a_w, const std::vector<long>& a_b,
+    const std::vector<long>& a_act, const std::vector<long>& c_in,
+    const std::vector<long>& c_out, const std::vector<long>& c_w,
+    const std::vector<long>& c_b, const std::vector<long>& c_act, long N,
+    long n, long M, at::ScalarType dtype) {
+  PpoPlan pl;
+  auto no = [&](std::string why) -> PpoPlan& {
+    pl.why = std::move(why);
+    return pl;
+  };
+  if (dtype != torch::kFloat && dtype != torch::kDouble) {
+    return no("dtype must be float32 or float64");
+  }
+  const long esz = dtype == torch::kDouble ? 8 : 4;
+  const long TM = dtype == torch::kDouble
+      ? ppof::tile_rows<double>::value : ppof::tile_rows<float>::value;
+  if (N < 1 || N > 65535 || M < 1 || N * M >= (1L << 27)) {
+    return no("needs 1 <= N <= 65535 nodes and N*M < 2^27 rows");
+  }
+  if (n < 1 || n >= (1L << 31)) return no("parameter row too long");
+  const std::vector<long>* ls[2][5] = {
+      {&a_in, &a_out, &a_w, &a_b, &a_act},
+      {&c_in, &c_out, &c_w, &c_b, &c_act}};
+  auto p16 = [](long v) { return (v + 15) / 16 * 16; };
+  ppof::Prog& pg = pl.prog;
+  pg.dz[0] = 0;
+  pg.dz[1] = (int)(TM * ppof::LDZ);
+  long lds_el = 0, slab = 0;
+  for (int k = 0; k < 2; ++k) {
+    const char* who = k == 0 ? "actor" : "critic";
+    const auto& in = *ls[k][0];
+    const auto& out = *ls[k][1];
+    const auto& wo = *ls[k][2];
+    const auto& bo = *ls[k][3];
+    const auto& act = *ls[k][4];
+    const long nl = (long)in.size();
+    if (nl < 1 || nl > ppof::MAXL) {
+      return no(std::string(who) + " must have 1 to " +
+                std::to_string(ppof::MAXL) + " linear layers");
+    }
+    if ((long)out.size() != nl || (long)wo.size() != nl ||
+        (long)bo.size() != nl || (long)act.size() != nl) {
+      return no("layer lists differ in length");
+    }
+    ppof::Net& nt = pg.net[k];
+    nt.nl = (int)nl;
+    long cur = 2 * TM * ppof::LDZ, lo = n, hi = 0, sum = 0;
+    for (long i = 0; i < nl; ++i) {
+      const long I = in[i], O = out[i];
+      if (I < 1 || O < 1 || I > ppof::MAX_W || O > ppof::MAX_W) {
+        return no(std::string(who) + " layer widths must be 1 to " +
+                  std::to_string(ppof::MAX_W));
+      }
+      if (I != (i == 0 ? (*ls[0][0])[0] : out[i - 1])) {
+        return no(std::string(who) + " layer " + std::to_string(i) +
+                  " does not take the layer below's output");
+      }
+      if (act[i] != (i == nl - 1 ? ACT_NONE : ACT_RELU)) {
+        return no("hidden activations must be relu and the output "
+                  "layer linear");
+      }
+      if (wo[i] < 0 || bo[i] < 0 || wo[i] + I * O > n || bo[i] + O > n) {
+        return no(std::string(who) + " layer " + std::to_string(i) +
+                  " lies outside the parameter row");
+      }
+      nt.in_dim[i] = (int)I; nt.out_dim[i] = (int)O;
+      nt.w_off[i] = (int)wo[i]; nt.b_off[i] = (int)bo[i];
+      lo = std::min({lo, wo[i], bo[i]});
+      hi = std::max({hi, wo[i] + I * O, bo[i] + O});
+      sum += I * O + O;
+      // the layer's input image, weight image and bias
+      nt.aimg[i] = (int)cur; cur += TM * (p16(I) + 2);
+      nt.wimg[i] = (int)cur; cur += p16(O) * (p16(I) + 2);
+      nt.bimg[i] = (int)cur; cur += p16(O);
+    }
+    // the reducer overwrites [base, base + span) from slabs in which
+    // every word is some layer's: no gaps
+    if (hi - lo != sum) {
+      return no(std::string(who) +
+                " layers must tile one contiguous slice of the row");
+    }
+    nt.base = (int)lo;
+    nt.span = (int)sum;
+    slab = std::max(slab, sum + 1);
+    lds_el = std::max(lds_el, cur);
+  }
+  if (a_out.back() > losses::PPO_MAX_A) {
+    return no("action dim must be <= " +
+              std::to_string(losses::PPO_MAX_A));
+  }
+  if (c_out.back() != 1) return no("the critic's head must be 1 wide");
+  pg.slab = (int)slab;
+  pl.lds = lds_el * esz;
+  if (pl.lds + ppof::STATIC_LDS > ppof::LDS_BUDGET) {
+    return no("the nets' LDS images need " + std::to_string(pl.lds) +
+              " bytes, over the " +
+              std::to_string(ppof::LDS_BUDGET - ppof::STATIC_LDS) +
+              " of one block");
+  }
+  return pl;
+}
+
+bool ppo_grads_fusable(
+    std::vector<long> a_in, std::vector<long> a_out,
+    std::vector<long> a_w, std::vector<long> a_b,
+    std::vector<long> a_act, std::vector<long> c_in,
+    std::vector<long> c_out, std::vector<long> c_w,
+    std::vector<long> c_b, std::vector<long> c_act, long N, long n,
+    long M, at::ScalarType dtype) {
+  return ppo_grads_plan(a_in, a_out, a_w, a_b, a_act, c_in, c_out, c_w,
+                        c_b, c_act, N, n, M, dtype).why.empty();
+}
+
+std::string ppo_grads_limit(
+    std::vector<long> a_in, std::vector<long> a_out,
+    std::vector<long> a_w, std::vector<long> a_b,
+    std::vector<long> a_act, std::vector<long> c_in,
+    std::vector<long> c_out, std::vector<long> c_w,
+    std::vector<long> c_b, std::vector<long> c_act, long N, long n,
+    long M, at::ScalarType dtype) {
+  return ppo_grads_plan(a_in, a_out, a_w, a_b, a_act, c_in, c_out, c_w,
+                        c_b, c_act, N, n, M, dtype).why;
+}
+
+// ppo_grad_fused_k's workspace per device: the dW/db/loss slabs
+// [N, 2, tiles, slab] and one int32 ticket per (node, net). As with
+// FcSplitWs: no per-call memset (the tickets are zero when allocated and
+// every launch's reducers leave them zero), grown on demand, never freed.
+struct PpoFusedWs {
+  torch::Tensor slabs, tickets;
+};
+
+PpoFusedWs& ppo_fused_ws(const torch::Tensor& like, long slab_elems,
+                         long ntickets) {
+  static auto* ws = new std::map<int, PpoFusedWs>();
+  PpoFusedWs& w = (*ws)[like.get_device()];
+  const long need = slab_elems * (long)like.element_size();
+  if (!w.slabs.defined() || w.slabs.numel() < need) {
+    w.slabs = torch::empty({need}, like.options().dtype(torch::kUInt8));
+  }
+  if (!w.tickets.defined() || w.tickets.numel() < ntickets) {
+    w.tickets =
+        torch::zeros({ntickets}, like.options().dtype(torch::kInt32));
+  }
+  return w;
+}
+
+// grad [N, n] and loss [N, 2] (actor term, critic term; unscaled means)
+// are overwritten, both nets' slices of every row; neither needs to be
+// zero on entry. obs/acts [N*M, .], the rest [N*M], all of theta's
+// dtype.
+void ppo_grads_fused(
+    torch::Tensor theta, torch::Tensor obs, torch::Tensor acts,
+    torch::Tensor old_logp, torch::Tensor adv, torch::Tensor vtarg,
+    torch::Tensor grad, torch::Tensor loss, std::vector<long> a_in,
+    std::vector<long> a_out, std::vector<long> a_w,
+    std::vector<long> a_b, std::vector<long> a_act,
+    std::vector<long> c_in, std::vector<long> c_out,
+    std::vector<long> c_w, std::vector<long> c_b,
+    std::vector<long> c_act, long M, double cov, double clip,
+    double critic_coef, double loss_scale) {
+  CHECK_DEV(theta); CHECK_DEV(obs); CHECK_DEV(acts); CHECK_DEV(old_logp);
+  CHECK_DEV(adv); CHECK_DEV(vtarg); CHECK_DEV(grad); CHECK_DEV(loss);
+  TORCH_CHECK(theta.dim() == 2, "theta must be the [N, n] stack");
+  const long N = theta.size(0), n = theta.size(1);
+  PpoPlan pl = ppo_grads_plan(a_in, a_out, a_w, a_b, a_act, c_in, c_out,
+                              c_w, c_b, c_act, N, n, M,
+                              theta.scalar_type());
+  TORCH_CHECK(pl.why.empty(), "ppo_grads_fused: ", pl.why,
+              " (ppo_grads_fusable decides)");
+  TORCH_CHECK(cov > 0, "cov must be positive");
+  const long A = a_out.back(), obs_dim = a_in[0], rows = N * M;
+  TORCH_CHECK(grad.dim() == 2 && grad.size(0) == N && grad.size(1) == n,
+              "grad must be [N, n] like theta");
+  TORCH_CHECK(loss.numel() == 2 * N, "loss must be [N, 2]");
+  TORCH_CHECK(obs.numel() == rows * obs_dim && acts.numel() == rows * A,
+              "obs / acts must be [N*M, obs_dim] / [N*M, A]");
+  for (const torch::Tensor* t : {&old_logp, &adv, &vtarg}) {
+    TORCH_CHECK(t->numel() == rows, "per-sample vectors must be [N*M]");
+  }
+  for (const torch::Tensor* t :
+       {&obs, &acts, &old_logp, &adv, &vtarg, &grad, &loss}) {
+    TORCH_CHECK(t->scalar_type() == theta.scalar_type(),
+                "ppo_grads_fused tensors must share theta's dtype");
+  }
+  const double logc =
+      0.5 * (double)A * std::log(2.0 * 3.14159265358979323846 * cov);
+  DISPATCH_FT(theta, {
+    constexpr int TM = ppof::tile_rows<scalar_t>::value;
+    const long tiles = (M + TM - 1) / TM;
+    PpoFusedWs& ws =
+        ppo_fused_ws(theta, N * 2 * tiles * (long)pl.prog.slab, N * 2);
+    const void* fn = reinterpret_cast<const void*>(
+        ppof::ppo_grad_fused_k<scalar_t, TM>);
+    static bool lds_raised = false;  // once per dtype: > 64 KB of LDS
+    if (!lds_raised) {
+      TORCH_CHECK(hipFuncSetAttribute(
+                      fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                      ppof::LDS_BUDGET - ppof::STATIC_LDS) == hipSuccess,
+                  "ppo_grads_fused: cannot raise the dynamic LDS limit");
+      lds_raised = true;
+    }
+    hipLaunchKernelGGL((ppof::ppo_grad_fused_k<scalar_t, TM>),
+        dim3(tiles, 2, N), dim3(256), (size_t)pl.lds, cur_stream(),
+        theta.data_ptr<scalar_t>(), obs.data_ptr<scalar_t>(),
+        acts.data_ptr<scalar_t>(), old_logp.data_ptr<scalar_t>(),
+        adv.data_ptr<scalar_t>(), vtarg.data_ptr<scalar_t>(),
+        grad.data_ptr<scalar_t>(), loss.data_ptr<scalar_t>(),
+        reinterpret_cast<scalar_t*>(ws.slabs.data_ptr()),
+        ws.tickets.data_ptr<int>(), pl.prog, n, (int)M, (int)A,
+        (scalar_t)(1.0 / cov), (scalar_t)logc, (scalar_t)(1.0 - clip),
+        (scalar_t)(1.0 + clip), (scalar_t)critic_coef,
+        (scalar_t)loss_scale);
   });
   HIP_CHECK_LAST();
 }
@@ -2253,6 +2485,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("rtgs"), py::arg("ep_rew"), py::arg("M"),
           py::arg("ep_len"), py::arg("cov"), py::arg("gamma"),
           py::arg("envp"), py::arg("last_obs") = py::none());
+  mod.def("ppo_grads_fusable", &ppo_grads_fusable);
+  mod.def("ppo_grads_limit", &ppo_grads_limit);
+  mod.def("ppo_grads_fused", &ppo_grads_fused);
   mod.def("ppo_gae", &ppo_gae, py::arg("v"), py::arg("rews"),
           py::arg("rew_stride"), py::arg("adv"), py::arg("ret"),
           py::arg("M"), py::arg("ep_len"), py::arg("gamma"),

@@ -52,20 +52,21 @@ class _PPOBase:
 
     # ------------------------------------------------------------------
     def _resolve_grad_engine(self):
-        """The StackedPPOEngine for ``grad_engine: "stacked"``, None for
-        ``"torch"``. A stacked request that cannot be served is an
-        error, never a quiet per-node run."""
+        """The StackedPPOEngine for ``grad_engine: "stacked"``, the
+        FusedPPOEngine (its one-launch ``grads``) for ``"fused"``, None
+        for ``"torch"``. A stacked or fused request that cannot be
+        served is an error, never a quiet per-node run."""
         if self.grad_engine == "torch":
             return None
-        if self.grad_engine != "stacked":
+        if self.grad_engine not in ("stacked", "fused"):
             raise ValueError(
-                f"grad_engine must be 'torch' or 'stacked', got "
+                f"grad_engine must be 'torch', 'stacked' or 'fused', got "
                 f"{self.grad_engine!r}"
             )
         if self.device.type != "cuda":
             raise ValueError(
-                "grad_engine='stacked' needs a GPU problem; this one is "
-                f"on {self.device}"
+                f"grad_engine={self.grad_engine!r} needs a GPU problem; "
+                f"this one is on {self.device}"
             )
         from ..ops import get_ext
 
@@ -73,12 +74,15 @@ class _PPOBase:
             get_ext()
         except Exception as e:  # noqa: BLE001
             raise ValueError(
-                "grad_engine='stacked' needs the HIP extension, which "
-                f"failed to load: {e}"
+                f"grad_engine={self.grad_engine!r} needs the HIP "
+                f"extension, which failed to load: {e}"
             ) from e
-        from .stacked_ppo import StackedPPOEngine
+        from .stacked_ppo import FusedPPOEngine, StackedPPOEngine
 
-        engine = StackedPPOEngine(self.pr)
+        engine = (
+            FusedPPOEngine if self.grad_engine == "fused"
+            else StackedPPOEngine
+        )(self.pr)
         # rollout() takes V(obs) for the advantages from the engine
         self.pr.value_engine = engine
         return engine

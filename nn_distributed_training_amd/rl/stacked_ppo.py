@@ -7,6 +7,9 @@ node) becomes a fixed sequence of launches for ALL nodes: every node's
 ``DistPPOProblem.node_vector``), both nets run through the stacked
 linear kernels, and ``ext.ppo_loss_bwd`` (ops/hip/losses.hip) turns the
 two nets' outputs into the gradients with respect to them.
+:class:`FusedPPOEngine` computes the same rows in ONE launch
+(``ext.ppo_grads_fused``, ops/hip/ppo_fused.hip) for nets that fit its
+limits.
 
 :func:`ppo_loss_grads_torch` is the kernel's formula in plain torch: the
 documentation of what the kernel computes and the oracle of the CPU
@@ -319,3 +322,46 @@ class StackedPPOEngine:
         """``[N, 2]`` (actor term, critic term) of the last
         :meth:`grads` call."""
         return self._loss
+
+
+class FusedPPOEngine(StackedPPOEngine):
+    """``grads`` as ONE launch for all nodes (``ppo_grad_fused_k``:
+    both nets' forward, the loss and the whole backward in LDS, a
+    deterministic cross-tile reduce that overwrites ``grad`` and the
+    loss buffer). Everything else - the ``[N, n]`` layout, ``values``,
+    ``values_last``, the ``load_*`` methods, ``losses`` - is the stacked
+    engine's, so rollouts and advantages run unchanged. Nets outside the
+    kernel's limits (``ext.ppo_grads_fusable``) are refused here, never
+    run another way."""
+
+    def __init__(self, problem):
+        super().__init__(problem)
+
+        def lists(plan):
+            return (
+                [layer.in_dim for layer in plan],
+                [layer.out_dim for layer in plan],
+                [layer.w_off for layer in plan],
+                [layer.b_off for layer in plan],
+                [ACT_IDS[layer.activation] for layer in plan],
+            )
+
+        self._plans = lists(self.actor_plan) + lists(self.critic_plan)
+        # every limit but the row count, which grads() checks per batch
+        shape = (self.N, self.n, 1, self.dtype)
+        if not self.ext.ppo_grads_fusable(*self._plans, *shape):
+            raise ValueError(
+                "grad_engine='fused' cannot run these nets: "
+                + self.ext.ppo_grads_limit(*self._plans, *shape)
+            )
+
+    def grads(self, theta=None, loss_scale=1.0):
+        theta = self._check_theta(theta)
+        conf = self.pr.conf
+        self.ext.ppo_grads_fused(
+            theta, self.obs, self.acts, self.old_logp, self.adv,
+            self.vtarg, self.grad, self._loss, *self._plans, self.M,
+            float(conf["cov"]), float(conf["clip"]),
+            float(conf["critic_coef"]), float(loss_scale),
+        )
+        return self.grad

@@ -55,9 +55,12 @@ def build_parser():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--out", default="./trained")
     p.add_argument(
-        "--grad-engine", default="torch", choices=["torch", "stacked"],
-        help="PPO gradients by per-node autograd (torch) or batched "
-             "over all nodes on the HIP kernels (stacked; needs a GPU)",
+        "--grad-engine", default="torch",
+        choices=["torch", "stacked", "fused"],
+        help="PPO gradients by per-node autograd (torch), batched over "
+             "all nodes on the HIP linear kernels (stacked; needs a GPU) "
+             "or in one HIP launch for all nodes (fused; needs a GPU, "
+             "layer widths <= 64)",
     )
     p.add_argument(
         "--rollout-engine", default="host", choices=["host", "device"],

@@ -10,12 +10,13 @@ seeded rollout buffers:
              gradient concatenation and the set_node_vector write-back
              the loop needs every primal iteration;
   "stacked": StackedPPOEngine.grads (batched kernels, no autograd);
+  "fused":   FusedPPOEngine.grads (one launch for all nodes);
 * one full DiNNO step_round (dual ascent + primal_iterations steps) with
-  grad_engine "torch" and "stacked".
+  grad_engine "torch", "stacked" and "fused".
 
 Every figure is a host clock around a window of --iters calls that ends
 in a device synchronize, after --warmup untimed calls; the window is
-repeated --repeats times, the two variants alternating, and the median
+repeated --repeats times, the variants alternating, and the median
 with the min-max spread is reported. Prints one JSON line per dtype.
 
 Run: python tools/bench_ppo_grads.py [--iters 100 --repeats 7]
@@ -98,14 +99,18 @@ def bench_dtype(dtype, args):
     hidden = tuple(args.hidden)
     pr_t = make_problem(args.nodes, args.samples, hidden, dev)
     pr_s = copy.deepcopy(pr_t)
+    pr_f = copy.deepcopy(pr_t)
     conf = {"verbose": False, "primal_iterations": args.primal_iterations,
             "rho_init": 0.3, "primal_lr_start": 1e-4,
             "primal_lr_finish": 1e-4, "lr_decay_type": "constant"}
     o_t = DiNNOPPO(pr_t, {**conf, "grad_engine": "torch"})
     o_s = DiNNOPPO(pr_s, {**conf, "grad_engine": "stacked"})
+    o_f = DiNNOPPO(pr_f, {**conf, "grad_engine": "fused"})
     o_s._begin_round()
+    o_f._begin_round()
     theta_t = o_t._theta_stack()
     theta_s = o_s._theta_stack()
+    theta_f = o_f._theta_stack()
 
     def grads_torch():
         o_t._grad_stack(theta_t)
@@ -115,15 +120,22 @@ def bench_dtype(dtype, args):
     def grads_stacked():
         o_s._grad_stack(theta_s)
 
-    # same numbers from both before any timing
+    def grads_fused():
+        o_f._grad_stack(theta_f)
+
+    # same numbers from all three before any timing
     g_t = o_t._grad_stack(theta_t)
     g_s = o_s._grad_stack(theta_s)
+    g_f = o_f._grad_stack(theta_f)
     dev_max = (g_t - g_s).abs().max().item()
+    dev_max_fused = (g_t - g_f).abs().max().item()
 
-    g = compare({"torch": grads_torch, "stacked": grads_stacked},
+    g = compare({"torch": grads_torch, "stacked": grads_stacked,
+                 "fused": grads_fused},
                 args.iters, args.warmup, args.repeats)
     r = compare({"torch": lambda: o_t.step_round(0),
-                 "stacked": lambda: o_s.step_round(0)},
+                 "stacked": lambda: o_s.step_round(0),
+                 "fused": lambda: o_f.step_round(0)},
                 max(1, args.iters // args.primal_iterations),
                 max(2, args.warmup // args.primal_iterations),
                 args.repeats)
@@ -139,11 +151,16 @@ def bench_dtype(dtype, args):
         "primal_iterations": args.primal_iterations,
         "iters": args.iters, "repeats": args.repeats,
         "max_abs_grad_diff": dev_max,
+        "max_abs_grad_diff_fused": dev_max_fused,
         "grads": {k: row(x) for k, x in g.items()},
         "grads_speedup": round(g["torch"][0] / g["stacked"][0], 2),
+        "grads_fused_vs_stacked": round(
+            g["stacked"][0] / g["fused"][0], 2),
         "dinno_round": {k: row(x) for k, x in r.items()},
         "dinno_round_speedup": round(
             r["torch"][0] / r["stacked"][0], 2),
+        "dinno_round_fused_vs_stacked": round(
+            r["stacked"][0] / r["fused"][0], 2),
     }
     print(json.dumps(out), flush=True)
     return out

@@ -15,6 +15,7 @@
 #include "advantage.hip"
 #include "fused_mnist.hip"
 #include "ppo_fused.hip"
+#include "mlp_grad_fused.hip"
 
 #include <ATen/hip/HIPContext.h>
 
@@ -2259,6 +2260,174 @@ void mlp_fwd_fused(torch::Tensor spec, torch::Tensor scales,
   HIP_CHECK_LAST();
 }
 
+// ---- whole gradient row in one launch (mlp_grad_fused.hip) ------------
+// mlp_grad_plan is the one place that decides whether mlp_grad_fused_k
+// takes a chain and lays out its LDS: what mlp_plan accepts, narrowed to
+// lift + trunk(s) + tail with the activations the backward phases know,
+// a regression loss_kind, and weight / bias slices that tile [0, end)
+// (n >= 0: end == n), so that writing them is writing the row.
+struct MlpGradPlan {
+  bool ok = false;
+  mlpg::Prog prog = {};
+  long lds = 0;
+};
+
+MlpGradPlan mlp_grad_plan(const torch::Tensor& spec, long M,
+                          long gemm_prec, at::ScalarType dtype,
+                          long loss_kind, long n = -1) {
+  MlpGradPlan gp;
+  const MlpPlan fp = mlp_plan(spec, M, gemm_prec, dtype);
+  if (!fp.ok || !fp.prog.has_tail || loss_kind < 1 || loss_kind > 3) {
+    return gp;
+  }
+  mlpg::Prog& pg = gp.prog;
+  pg.f = fp.prog;
+  const int nl = pg.f.nl, nt = nl - 2;
+  std::vector<std::pair<long, long>> slices;
+  for (int li = 0; li < nl; ++li) {
+    const mlpf::Layer& y = pg.f.ly[li];
+    const int a = y.act;
+    const bool act_ok =
+        li == 0 ? (a == ACT_SIN_RELU || a == ACT_RELU || a == ACT_NONE)
+        : li <= nt ? (a == ACT_RELU || a == ACT_NONE)
+                   : (a == ACT_NONE || a == ACT_SIGMOID || a == ACT_TANH);
+    if (!act_ok) return gp;
+    slices.push_back({y.w_off, (long)y.in * y.out});
+    slices.push_back({y.b_off, (long)y.out});
+    pg.vec[li] = (y.w_off % 4 == 0 && y.in % 4 == 0) ? 1 : 0;
+  }
+  if (loss_kind == 1 && pg.f.ly[nl - 1].act != ACT_SIGMOID) return gp;
+  std::sort(slices.begin(), slices.end());
+  long end = 0;
+  for (const auto& s : slices) {
+    if (s.first != end) return gp;
+    end += s.second;
+  }
+  if ((n >= 0 && end != n) || end >= (1L << 30)) return gp;
+  pg.nt = nt;
+  pg.loss_kind = (int)loss_kind;
+  pg.slab = (int)((end + 1 + 3) / 4 * 4);
+  // the weight images and the wide image stay where mlp_plan put them
+  const long par_bytes = fp.lds - pg.f.off_par;
+  pg.off_act = pg.f.off_wide + mlpf::TM * mlpf::LDW * 2;
+  pg.off_dz = pg.off_act + (nt - 1) * mlpg::IMG_N;
+  pg.f.off_narrow = pg.off_act;
+  pg.f.off_tail = pg.off_dz + 2 * mlpg::IMG_N;
+  pg.off_x = pg.f.off_tail + mlpf::TM * mlpf::LDT * 4;
+  pg.off_hz = pg.off_x + mlpf::TM * 4 * 4;
+  pg.off_red = pg.off_hz + mlpf::TM * 4 * 4;
+  pg.f.off_par = pg.off_red + mlpg::RED_FLOATS * 4;
+  gp.lds = pg.f.off_par + par_bytes;
+  gp.ok = gp.lds <= mlpf::LDS_BUDGET;
+  return gp;
+}
+
+bool mlp_grads_fusable(torch::Tensor spec, long M, long gemm_prec,
+                       at::ScalarType dtype, long loss_kind) {
+  return mlp_grad_plan(spec, M, gemm_prec, dtype, loss_kind).ok;
+}
+
+// mlp_grad_fused_k's workspace per device: the gradient slabs [L, J,
+// slab] and one int32 ticket per node. As with PpoFusedWs: no per-call
+// memset (the tickets are zero when allocated and every launch's
+// reducers leave them zero), grown on demand, never freed.
+PpoFusedWs& mlp_grad_ws(const torch::Tensor& like, long slab_elems,
+                        long ntickets) {
+  static auto* ws = new std::map<int, PpoFusedWs>();
+  PpoFusedWs& w = (*ws)[like.get_device()];
+  if (!w.slabs.defined() || w.slabs.numel() < slab_elems) {
+    w.slabs = torch::empty({slab_elems}, like.options());
+  }
+  if (!w.tickets.defined() || w.tickets.numel() < ntickets) {
+    w.tickets =
+        torch::zeros({ntickets}, like.options().dtype(torch::kInt32));
+  }
+  return w;
+}
+
+// grad [L, n] and the optional loss [L] (unscaled per-node means) are
+// overwritten; neither needs to be zero on entry. xb [L*M, in], yb
+// [L*M, out] of the tail. max_blocks > 0 caps the persistent grid.
+void mlp_grads_fused(torch::Tensor spec, torch::Tensor scales,
+                     torch::Tensor xb, torch::Tensor yb,
+                     torch::Tensor theta, torch::Tensor grad,
+                     c10::optional<torch::Tensor> loss, long loss_kind,
+                     double loss_scale, long M, long max_blocks = 0) {
+  CHECK_DEV(xb); CHECK_DEV(yb); CHECK_DEV(theta); CHECK_DEV(grad);
+  TORCH_CHECK(theta.dim() == 2 && theta.is_contiguous() &&
+                  xb.is_contiguous() && yb.is_contiguous() &&
+                  grad.is_contiguous(),
+              "mlp_grads_fused: theta [L, n], grad, xb and yb must be "
+              "contiguous");
+  const long L = theta.size(0), n = theta.size(1);
+  MlpGradPlan gp = mlp_grad_plan(spec, M, 1, theta.scalar_type(),
+                                 loss_kind, n);
+  TORCH_CHECK(gp.ok && xb.scalar_type() == torch::kFloat &&
+                  yb.scalar_type() == torch::kFloat &&
+                  grad.scalar_type() == torch::kFloat,
+              "mlp_grads_fused: this chain, loss or stack is not fusable "
+              "(mlp_grads_fusable decides; the layers' slices must tile "
+              "the whole row)");
+  mlpg::Prog& pg = gp.prog;
+  const long nl = pg.f.nl;
+  TORCH_CHECK(scales.device().is_cpu() && scales.numel() == nl &&
+                  scales.scalar_type() == torch::kDouble,
+              "mlp_grads_fused: scales needs one entry per layer");
+  TORCH_CHECK(max_blocks >= 0 && L >= 1 &&
+                  xb.numel() == L * M * pg.f.ly[0].in &&
+                  yb.numel() == L * M * pg.f.ly[nl - 1].out,
+              "mlp_grads_fused: xb / yb must be [L*M, in] / [L*M, out]");
+  TORCH_CHECK(grad.dim() == 2 && grad.size(0) == L && grad.size(1) == n,
+              "mlp_grads_fused: grad must be [L, n] like theta");
+  float* loss_p = nullptr;
+  if (loss.has_value()) {
+    CHECK_DEV(*loss);
+    TORCH_CHECK(loss->scalar_type() == torch::kFloat &&
+                    loss->is_contiguous() && loss->numel() == L,
+                "mlp_grads_fused: loss must be fp32 [L]");
+    loss_p = loss->data_ptr<float>();
+  }
+  const auto sc = scales.accessor<double, 1>();
+  for (long li = 0; li < nl; ++li) {
+    pg.f.ly[li].scale = (float)sc[li];
+    pg.f.stash[li] = nullptr;
+  }
+  pg.w = (float)loss_scale / (float)M;
+  const long tpn = (M + mlpf::TM - 1) / mlpf::TM, total = L * tpn;
+  const long cap = max_blocks > 0
+      ? max_blocks
+      : at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  const long G = std::min(total, cap);
+  // the kernel's owner(): block b holds tiles [total*b/G, total*(b+1)/G)
+  auto owner = [&](long t) {
+    long b = t * G / total;
+    while (total * (b + 1) / G <= t) ++b;
+    while (total * b / G > t) --b;
+    return b;
+  };
+  long J = 1;
+  for (long l = 0; l < L; ++l) {
+    J = std::max(J, owner((l + 1) * tpn - 1) - owner(l * tpn) + 1);
+  }
+  pg.J = (int)J;
+  PpoFusedWs& ws = mlp_grad_ws(theta, L * J * (long)pg.slab, L);
+  static bool lds_raised = false;  // > 64 KB of LDS
+  if (!lds_raised) {
+    TORCH_CHECK(hipFuncSetAttribute(
+                    reinterpret_cast<const void*>(mlpg::mlp_grad_fused_k),
+                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                    (int)mlpf::LDS_BUDGET) == hipSuccess,
+                "mlp_grads_fused: cannot raise the dynamic LDS limit");
+    lds_raised = true;
+  }
+  hipLaunchKernelGGL(mlpg::mlp_grad_fused_k, dim3((unsigned)G), dim3(256),
+      (size_t)gp.lds, cur_stream(), xb.data_ptr<float>(),
+      yb.data_ptr<float>(), theta.data_ptr<float>(),
+      grad.data_ptr<float>(), loss_p, ws.slabs.data_ptr<float>(),
+      ws.tickets.data_ptr<int>(), pg, n, (int)M, (int)L);
+  HIP_CHECK_LAST();
+}
+
 // fuse (trailing, default 0): 1 = run a chain that mlp_fwd_fusable
 // accepts as the optional gather plus ONE mlp_fwd_fused launch; any
 // other chain, and fuse = 0, run the layered loop below unchanged. An
@@ -2518,6 +2687,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("mlp_fwd_fused", &mlp_fwd_fused, py::arg("spec"),
           py::arg("scales"), py::arg("xb"), py::arg("theta"),
           py::arg("acts"), py::arg("M"), py::arg("max_blocks") = 0);
+  mod.def("mlp_grads_fusable", &mlp_grads_fusable, py::arg("spec"),
+          py::arg("M"), py::arg("gemm_prec"), py::arg("dtype"),
+          py::arg("loss_kind"));
+  mod.def("mlp_grads_fused", &mlp_grads_fused, py::arg("spec"),
+          py::arg("scales"), py::arg("xb"), py::arg("yb"),
+          py::arg("theta"), py::arg("grad"), py::arg("loss"),
+          py::arg("loss_kind"), py::arg("loss_scale"), py::arg("M"),
+          py::arg("max_blocks") = 0);
   mod.def("bwd_chain", &bwd_chain, py::arg("spec"), py::arg("scales"),
           py::arg("xb"), py::arg("theta"), py::arg("grad"),
           py::arg("acts"), py::arg("zs"), py::arg("dzs"),

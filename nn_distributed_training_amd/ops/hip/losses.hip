@@ -56,27 +56,50 @@ __global__ void nll_bwd_k(
 // sigmoid+BCE combined backward (final density layer, O == 1):
 // p = sigmoid(z) is the layer's stored output; dZ = (p - t)/B directly
 // (the classic cancellation), loss[l] += BCE/B with clamped logs.
+// The per-element arithmetic is in bce_dz / bce_term (w = loss_scale / B),
+// which mlp_grad_fused.hip evaluates on its LDS-resident head as well.
+template <typename T>
+DEV_INLINE T bce_dz(T pm, T t, T w) {
+  return (pm - t) * w;
+}
+
+template <typename T>
+DEV_INLINE T bce_term(T pm, T t, int B) {
+  const T eps = T(1e-12);
+  const T lp = ::log(pm > eps ? pm : eps);
+  const T lq = ::log((T(1) - pm) > eps ? (T(1) - pm) : eps);
+  return -(t * lp + (T(1) - t) * lq) / T(B);
+}
+
 template <typename T>
 __global__ void bce_bwd_k(
     const T* __restrict__ p, const T* __restrict__ tgt,
     T* __restrict__ dZ, T* __restrict__ loss, long M, int B,
     T loss_scale) {
   const T w = loss_scale / T(B);
-  const T eps = T(1e-12);
   for (long m = blockIdx.x * 256L + threadIdx.x; m < M;
        m += (long)gridDim.x * 256L) {
     const T pm = p[m], t = tgt[m];
-    dZ[m] = (pm - t) * w;
-    if (loss != nullptr) {
-      const T lp = ::log(pm > eps ? pm : eps);
-      const T lq = ::log((T(1) - pm) > eps ? (T(1) - pm) : eps);
-      atomicAdd(&loss[m / B], -(t * lp + (T(1) - t) * lq) / T(B));
-    }
+    dZ[m] = bce_dz(pm, t, w);
+    if (loss != nullptr) atomicAdd(&loss[m / B], bce_term(pm, t, B));
   }
 }
 
 // MSE / L1 backward w.r.t. the final ACTIVATION output (caller chains
 // act_grad for the sigmoid). mode 0 = MSE, 1 = L1.
+// d = yhat - tgt, w = loss_scale / B; shared with mlp_grad_fused.hip.
+template <typename T, int MODE>
+DEV_INLINE T regression_dy(T d, T w) {
+  if (MODE == 0) return T(2) * d * w;
+  return d > T(0) ? w : (d < T(0) ? -w : T(0));
+}
+
+template <typename T, int MODE>
+DEV_INLINE T regression_term(T d, int B) {
+  if (MODE == 0) return d * d / T(B);
+  return (d > T(0) ? d : -d) / T(B);
+}
+
 template <typename T, int MODE>
 __global__ void regression_bwd_k(
     const T* __restrict__ yhat, const T* __restrict__ tgt,
@@ -86,14 +109,9 @@ __global__ void regression_bwd_k(
   for (long m = blockIdx.x * 256L + threadIdx.x; m < M;
        m += (long)gridDim.x * 256L) {
     const T d = yhat[m] - tgt[m];
-    if (MODE == 0) {
-      dY[m] = T(2) * d * w;
-      if (loss != nullptr) atomicAdd(&loss[m / B], d * d / T(B));
-    } else {
-      dY[m] = (d > T(0) ? w : (d < T(0) ? -w : T(0)));
-      if (loss != nullptr) {
-        atomicAdd(&loss[m / B], (d > T(0) ? d : -d) / T(B));
-      }
+    dY[m] = regression_dy<T, MODE>(d, w);
+    if (loss != nullptr) {
+      atomicAdd(&loss[m / B], regression_term<T, MODE>(d, B));
     }
   }
 }

@@ -265,8 +265,9 @@ DEV_INLINE void trunk_tile(const Prog& p, int li, unsigned char* lds,
   }
 }
 
-DEV_INLINE void tail_tile(const Prog& p, unsigned char* lds, long grow0,
-                          int m0, int M, int tid) {
+// the tail's output (row = tid>>2, q = tid&3) of the tile; every thread
+// of the block calls it (lane exchanges), q >= out gets padding
+DEV_INLINE float tail_out(const Prog& p, unsigned char* lds, int tid) {
   const Layer& y = p.ly[p.nl - 1];
   const float* par =
       reinterpret_cast<const float*>(lds + p.off_par) + y.par;
@@ -287,9 +288,16 @@ DEV_INLINE void tail_tile(const Prog& p, unsigned char* lds, long grow0,
   }
   const float z = (q == 0 ? s[0] : q == 1 ? s[1] : q == 2 ? s[2] : s[3])
                   + par[TAIL_OUT * 64 + q];
+  return act_fwd(y.act, z, y.scale);
+}
+
+DEV_INLINE void tail_tile(const Prog& p, unsigned char* lds, long grow0,
+                          int m0, int M, int tid) {
+  const Layer& y = p.ly[p.nl - 1];
+  const int row = tid >> 2, q = tid & 3;
+  const float v = tail_out(p, lds, tid);
   if (q < y.out && m0 + row < M) {
-    p.stash[p.nl - 1][(grow0 + m0 + row) * y.out + q] =
-        act_fwd(y.act, z, y.scale);
+    p.stash[p.nl - 1][(grow0 + m0 + row) * y.out + q] = v;
   }
 }
 

@@ -401,6 +401,29 @@ def resolve_fused_forward(conf, dtype, gemm_prec, env=None) -> bool:
     return on
 
 
+def resolve_fused_train(conf, dtype, gemm_prec, env=None) -> bool:
+    """Whether a training step asks for the one-launch gradient kernel
+    (ops/hip/mlp_grad_fused.hip), from the problem config's
+    ``fused_train`` key: false (default) or true, which needs the bf16
+    operands of ``gemm_precision: bf16``. Where the config does not set
+    the key, ``NDTA_FUSED_TRAIN=1`` in ``env`` turns it on under bf16
+    operands and is ignored otherwise. A model, loss or batch the kernel
+    cannot take (ext.mlp_grads_fusable) runs layered whatever the flag."""
+    env = os.environ if env is None else env
+    bf16 = gemm_prec == 1 and dtype == torch.float32
+    if "fused_train" not in conf:
+        return bf16 and env.get("NDTA_FUSED_TRAIN", "0") == "1"
+    on = conf["fused_train"]
+    if not isinstance(on, bool):
+        raise ValueError(f"fused_train must be true or false, got {on!r}")
+    if on and not bf16:
+        raise ValueError(
+            "fused_train: true runs the linear layers on bf16 operands "
+            "and needs gemm_precision: bf16"
+        )
+    return on
+
+
 class StackedEngine:
     def __init__(self, problem):
         self.ext = get_ext()
@@ -418,6 +441,11 @@ class StackedEngine:
         self.fused_fwd = resolve_fused_forward(
             problem.conf, self.dtype, self.gemm_prec
         )
+        # one-launch forward + loss + backward where the chain is fusable
+        self.fused_train = resolve_fused_train(
+            problem.conf, self.dtype, self.gemm_prec
+        )
+        self._fused_train_ok = None
 
         self.local_nodes = problem.local_nodes
         self.L = len(self.local_nodes)
@@ -761,6 +789,30 @@ class StackedEngine:
             and ls[2].out_dim <= 16
         )
 
+    def _regression_loss_kind(self):
+        """bwd_chain's / mlp_grads_fused's loss_kind of a regression
+        problem: 1 = sigmoid+BCE, 2 = MSE, 3 = L1."""
+        if (self._loss_kind == "BCELoss"
+                and self.spec.layers[-1].activation == "sigmoid"):
+            return 1
+        return 2 if self._loss_kind == "MSELoss" else 3
+
+    def _fused_train_applicable(self):
+        """fused_train is on, the problem is a regression problem and
+        ext.mlp_grads_fusable takes the training batch (asked once)."""
+        if self._fused_train_ok is None:
+            self._fused_train_ok = bool(
+                self.fused_train
+                and self._use_chain
+                and not self.classification
+                and self._loss_kind in ("BCELoss", "MSELoss", "L1Loss")
+                and self.ext.mlp_grads_fusable(
+                    self._chain_meta()[0], self.B, self.gemm_prec,
+                    self.dtype, self._regression_loss_kind(),
+                )
+            )
+        return self._fused_train_ok
+
     def fwd_bwd(self, xb, yb, loss_scale=1.0, want_loss=False,
                 graph_offs=None, pit=0, step=None):
         """Forward + backward for one primal iteration; takes the fused
@@ -816,6 +868,17 @@ class StackedEngine:
                 M, fc1.in_dim, fc1.out_dim, fc2.out_dim, loss_scale,
             )
             return loss_buf if want_loss else None
+        if graph_offs is None and self._fused_train_applicable():
+            # forward, loss and backward of every node in ONE launch; the
+            # kernel overwrites the grad stack and the loss row
+            spec_t, scales_t = self._chain_meta()
+            loss_buf = self._bufs["loss"] if want_loss else None
+            self.ext.mlp_grads_fused(
+                spec_t, scales_t, xb, yb, self.theta, self.grad, loss_buf,
+                self._regression_loss_kind(), loss_scale, self.B,
+            )
+            self.grad_is_zero = False
+            return loss_buf
         self.forward(xb, train_skip_logp=True)
         return self.backward(
             xb, yb, loss_scale=loss_scale, want_loss=want_loss,
@@ -891,13 +954,7 @@ class StackedEngine:
                 idx_off = 0 if graph_offs is not None else self._last_off
             else:
                 idx_t, stride, idx_off = None, 0, 0
-                if (self._loss_kind == "BCELoss"
-                        and last.activation == "sigmoid"):
-                    loss_kind = 1
-                elif self._loss_kind == "MSELoss":
-                    loss_kind = 2
-                else:
-                    loss_kind = 3
+                loss_kind = self._regression_loss_kind()
                 yb_arg = yb
             spec_t, scales_t = self._chain_meta()
             ext.bwd_chain(

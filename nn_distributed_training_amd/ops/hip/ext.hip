@@ -8,6 +8,7 @@
 #include "gemm.hip"
 #include "gemm_mfma.hip"
 #include "gemm_bf16.hip"
+#include "gemm_bf16_act.hip"
 #include "mlp_fused.hip"
 #include "conv.hip"
 #include "losses.hip"
@@ -312,17 +313,102 @@ inline bool use_bf16_gemm(long gemm_prec, const torch::Tensor& t,
   return gemm_prec == 1 && mfma_shape;
 }
 
+// MFMA pays only when M fills the 64-row tiles across the chip;
+// small-M layers (MNIST fc, per-node B=64) stay on the VALU kernels.
+// I must be even for the 16-byte staging loads (vec2 alignment).
+inline bool fwd_mfma_shape(long M, long I, long O) {
+  return M >= 128 && O >= 16 && I >= 8 && I % 2 == 0;
+}
+
+// the register-resident encode kernel's shapes (encode_fwd_k)
+inline bool fwd_encode_shape(long M, long I, long O) {
+  return !fwd_mfma_shape(M, I, O) && I <= 4 && M >= 1024 && O >= 64 &&
+         O <= 1024 && O % 64 == 0;
+}
+
+inline bool dx_mfma_shape(long M, long I, long O) {
+  return M >= 128 && I >= 16 && O >= 8 && I % 2 == 0 && O % 2 == 0;
+}
+
+inline bool is_bf16(const torch::Tensor& t) {
+  return t.scalar_type() == torch::kBFloat16;
+}
+
+// A bf16 X or Y: the activation-storage kernels of gemm_bf16_act.hip.
+// The storage type comes from the tensors; a shape, activation or Z
+// stash those kernels do not take is an error, never another path.
+void linear_fwd_act_bf16(const torch::Tensor& X, const torch::Tensor& theta,
+                         torch::Tensor& Y,
+                         const c10::optional<torch::Tensor>& Z, long w_off,
+                         long b_off, long M, long I, long O, long act,
+                         double scale, long gemm_prec) {
+  const bool xb = is_bf16(X), yb = is_bf16(Y);
+  const long L = theta.size(0), n = theta.size(1);
+  TORCH_CHECK(gemm_prec == 1 && theta.scalar_type() == torch::kFloat,
+              "bf16 activation storage needs gemm_prec = 1 and an fp32 "
+              "parameter stack");
+  TORCH_CHECK((xb || X.scalar_type() == torch::kFloat) &&
+                  (yb || Y.scalar_type() == torch::kFloat),
+              "bf16 activation storage: X and Y must be bf16 or fp32");
+  TORCH_CHECK(!Z.has_value(),
+              "bf16 activation storage: a layer with a Z stash keeps "
+              "fp32 storage");
+  TORCH_CHECK(X.is_contiguous() && Y.is_contiguous() &&
+                  X.numel() == L * M * I && Y.numel() == L * M * O,
+              "bf16 activation storage: X [L*M, I], Y [L*M, O] contiguous");
+  float* th = theta.data_ptr<float>();
+  if (!xb && fwd_encode_shape(M, I, O)) {
+    const long blocks = std::min<long>(M, 8192);
+    dim3 grid(blocks, 1, L);
+    auto launch_enc = [&](auto ik_tag) {
+      constexpr int IK = decltype(ik_tag)::value;
+      hipLaunchKernelGGL((gbf16a::encode_bf16_k<IK>), grid, dim3((int)O),
+          0, cur_stream(), X.data_ptr<float>(), th,
+          reinterpret_cast<__bf16*>(Y.data_ptr()), n, w_off, b_off,
+          (int)M, (int)O, (int)act, (float)scale);
+    };
+    if (I == 1) launch_enc(std::integral_constant<int, 1>{});
+    else if (I == 2) launch_enc(std::integral_constant<int, 2>{});
+    else if (I == 3) launch_enc(std::integral_constant<int, 3>{});
+    else launch_enc(std::integral_constant<int, 4>{});
+    HIP_CHECK_LAST();
+    return;
+  }
+  TORCH_CHECK(fwd_mfma_shape(M, I, O),
+              "bf16 activation storage: forward needs an MFMA shape "
+              "(M >= 128, O >= 16, I >= 8, I even) or the encode shape, "
+              "got M=", M, " I=", I, " O=", O);
+  TORCH_CHECK(!xb || I % 8 == 0,
+              "bf16 activation storage: a bf16 X needs I % 8 == 0");
+  TORCH_CHECK(!yb || O % 8 == 0,
+              "bf16 activation storage: a bf16 Y needs O % 8 == 0");
+  dim3 grid((O + 63) / 64, (M + 63) / 64, L);
+  auto launch = [&](auto xb_tag, auto yb_tag) {
+    hipLaunchKernelGGL(
+        (gbf16a::act_fwd_k<decltype(xb_tag)::value,
+                           decltype(yb_tag)::value>),
+        grid, dim3(256), 0, cur_stream(), X.data_ptr(), th, Y.data_ptr(),
+        n, w_off, b_off, (int)M, (int)I, (int)O, (int)act, (float)scale);
+  };
+  if (xb && yb) launch(std::true_type{}, std::true_type{});
+  else if (xb) launch(std::true_type{}, std::false_type{});
+  else launch(std::false_type{}, std::true_type{});
+  HIP_CHECK_LAST();
+}
+
 void linear_fwd(torch::Tensor X, torch::Tensor theta, torch::Tensor Y,
                 c10::optional<torch::Tensor> Z, long w_off, long b_off,
                 long M, long I, long O, long act, double scale,
                 long gemm_prec = 0) {
   CHECK_DEV(X); CHECK_DEV(theta); CHECK_DEV(Y);
+  if (is_bf16(X) || is_bf16(Y)) {
+    linear_fwd_act_bf16(X, theta, Y, Z, w_off, b_off, M, I, O, act, scale,
+                        gemm_prec);
+    return;
+  }
   const long L = theta.size(0), n = theta.size(1);
-  // MFMA pays only when M fills the 64-row tiles across the chip;
-  // small-M layers (MNIST fc, per-node B=64) stay on the VALU kernels.
-  // I must be even for the 16-byte staging loads (vec2 alignment).
-  const bool use_mfma = (M >= 128 && O >= 16 && I >= 8 && I % 2 == 0);
-  if (use_bf16_gemm(gemm_prec, X, use_mfma)) {
+  const bool use_mfma = fwd_mfma_shape(M, I, O);
+  if (use_bf16_gemm(gemm_prec, theta, use_mfma)) {
     dim3 grid((O + 63) / 64, (M + 63) / 64, L);
     hipLaunchKernelGGL(gbf16::bf16_fwd_k, grid, dim3(256), 0,
         cur_stream(), X.data_ptr<float>(), theta.data_ptr<float>(),
@@ -340,8 +426,7 @@ void linear_fwd(torch::Tensor X, torch::Tensor theta, torch::Tensor Y,
           X.data_ptr<scalar_t>(), theta.data_ptr<scalar_t>(),
           Y.data_ptr<scalar_t>(), zp, n, w_off, b_off,
           (int)M, (int)I, (int)O, (int)act, (scalar_t)scale);
-    } else if (I <= 4 && M >= 1024 && O >= 64 && O <= 1024 &&
-               O % 64 == 0) {
+    } else if (fwd_encode_shape(M, I, O)) {
       // register-resident encode kernel: one thread per output
       // column (blockDim == O), W row + bias in registers, scalar
       // X-row loads, compile-time-I guard-free dot
@@ -408,12 +493,47 @@ void linear_bwd_dx(torch::Tensor dZ, torch::Tensor theta,
                    long gemm_prec = 0) {
   CHECK_DEV(dZ); CHECK_DEV(dX);
   const long L = theta.size(0), n = theta.size(1);
-  const bool use_mfma =
-      (M >= 128 && I >= 16 && O >= 8 && I % 2 == 0 && O % 2 == 0);
+  const bool use_mfma = dx_mfma_shape(M, I, O);
   TORCH_CHECK(act_below == 0 || Yb.has_value(), "act_below needs Yb");
   TORCH_CHECK(!Xb2.has_value() || Ib <= 4,
               "z-recompute supports below-layer in_dim <= 4");
-  if (use_bf16_gemm(gemm_prec, dZ, use_mfma)) {
+  if (Yb.has_value() && is_bf16(*Yb)) {
+    // bf16 activation storage (gemm_bf16_act.hip): the mask comes from
+    // the bf16 bits; what act_dx_k does not take is an error
+    CHECK_DEV(*Yb);
+    TORCH_CHECK(gemm_prec == 1 && theta.scalar_type() == torch::kFloat &&
+                    dZ.scalar_type() == torch::kFloat &&
+                    dX.scalar_type() == torch::kFloat,
+                "bf16 activation storage needs gemm_prec = 1 and fp32 "
+                "theta, dZ and dX");
+    TORCH_CHECK(use_mfma && I % 8 == 0,
+                "bf16 activation storage: dX needs an MFMA shape "
+                "(M >= 128, I >= 16, O >= 8, both even) and I % 8 == 0, "
+                "got M=", M, " I=", I, " O=", O);
+    TORCH_CHECK(act_below == ACT_NONE || act_below == ACT_RELU ||
+                    (act_below == ACT_SIN_RELU && Xb2.has_value() &&
+                     !Zb.has_value()),
+                "bf16 activation storage: the layer below must be relu, "
+                "none, or sin_relu with z recomputed (in_dim <= 4); "
+                "sigmoid / tanh read y and keep fp32 storage");
+    TORCH_CHECK(!Xb2.has_value() || Xb2->scalar_type() == torch::kFloat,
+                "bf16 activation storage: Xb2 must be fp32");
+    TORCH_CHECK(Yb->is_contiguous() && Yb->numel() == L * M * I &&
+                    dZ.is_contiguous() && dX.is_contiguous() &&
+                    dZ.numel() == L * M * O && dX.numel() == L * M * I,
+                "bf16 activation storage: dZ [L*M, O], dX and Yb "
+                "[L*M, I] contiguous");
+    dim3 grid((I + 63) / 64, (M + 63) / 64, L);
+    hipLaunchKernelGGL(gbf16a::act_dx_k, grid, dim3(256), 0, cur_stream(),
+        dZ.data_ptr<float>(), theta.data_ptr<float>(),
+        dX.data_ptr<float>(),
+        reinterpret_cast<const __bf16*>(Yb->data_ptr()), (int)act_below,
+        (float)scale_below, n, w_off, (int)M, (int)I, (int)O,
+        opt_ptr<float>(Xb2), wb_off, bb_off, (int)Ib);
+    HIP_CHECK_LAST();
+    return;
+  }
+  if (use_bf16_gemm(gemm_prec, theta, use_mfma)) {
     dim3 grid((I + 63) / 64, (M + 63) / 64, L);
     hipLaunchKernelGGL(gbf16::bf16_dx_k, grid, dim3(256), 0,
         cur_stream(), dZ.data_ptr<float>(), theta.data_ptr<float>(),
@@ -499,7 +619,23 @@ void linear_bwd_dw(torch::Tensor dZ, torch::Tensor X,
                    long M, long I, long O, long gemm_prec = 0) {
   CHECK_DEV(dZ); CHECK_DEV(X); CHECK_DEV(gstack);
   const long L = gstack.size(0), n = gstack.size(1);
-  if (use_bf16_gemm(gemm_prec, dZ, dw_mfma_shape(M, I, O))) {
+  const bool xbf = is_bf16(X);
+  if (xbf) {
+    // bf16 activation storage (gemm_bf16_act.hip act_dw_k)
+    TORCH_CHECK(gemm_prec == 1 && gstack.scalar_type() == torch::kFloat &&
+                    dZ.scalar_type() == torch::kFloat,
+                "bf16 activation storage needs gemm_prec = 1 and fp32 "
+                "dZ and grad");
+    TORCH_CHECK(dw_mfma_shape(M, I, O) && I % 8 == 0,
+                "bf16 activation storage: dW needs an MFMA shape "
+                "(M >= 256, I >= 16, O >= 16) and I % 8 == 0, got M=", M,
+                " I=", I, " O=", O);
+    TORCH_CHECK(X.is_contiguous() && X.numel() == L * M * I &&
+                    dZ.is_contiguous() && dZ.numel() == L * M * O,
+                "bf16 activation storage: dZ [L*M, O], X [L*M, I] "
+                "contiguous");
+  }
+  if (use_bf16_gemm(gemm_prec, gstack, dw_mfma_shape(M, I, O))) {
     // M chunks of whole 64-row stages, about 1024 blocks in all; the
     // last chunk alone is ragged and none is empty, so every slab
     // element is written
@@ -519,10 +655,17 @@ void linear_bwd_dw(torch::Tensor dZ, torch::Tensor X,
     const long pstride = joint ? O * I + O : O * I;
     const long dbstride = joint ? O * I + O : O;
     dim3 grid((I + 63) / 64, (O + 63) / 64, L * nchunk);
-    hipLaunchKernelGGL(gbf16::bf16_dw_k, grid, dim3(256), 0,
-        cur_stream(), dZ.data_ptr<float>(), X.data_ptr<float>(), pp,
-        dbp, pstride, dbstride, (int)M, (int)I, (int)O, (int)mc,
-        (int)nchunk);
+    if (xbf) {
+      hipLaunchKernelGGL(gbf16a::act_dw_k, grid, dim3(256), 0,
+          cur_stream(), dZ.data_ptr<float>(),
+          reinterpret_cast<const __bf16*>(X.data_ptr()), pp, dbp, pstride,
+          dbstride, (int)M, (int)I, (int)O, (int)mc, (int)nchunk);
+    } else {
+      hipLaunchKernelGGL(gbf16::bf16_dw_k, grid, dim3(256), 0,
+          cur_stream(), dZ.data_ptr<float>(), X.data_ptr<float>(), pp,
+          dbp, pstride, dbstride, (int)M, (int)I, (int)O, (int)mc,
+          (int)nchunk);
+    }
     hipLaunchKernelGGL(gmfma::dw_reduce_parts_k<float>,
         dim3(grid_1d(pstride), 1, L), dim3(256), 0, cur_stream(),
         pp, gstack.data_ptr<float>(), n, w_off, pstride, (int)nchunk);
@@ -2428,6 +2571,40 @@ void mlp_grads_fused(torch::Tensor spec, torch::Tensor scales,
   HIP_CHECK_LAST();
 }
 
+// Whether the engine stores layer li's activation as bf16 (the kernels
+// of gemm_bf16_act.hip): only where the producer is one of those
+// kernels and EVERY consumer already rounds the buffer to bf16, so the
+// stored bits are the operands the fp32 buffer would have given. The
+// engine asks here (ops/stacked.py _alloc_bufs) instead of re-deriving.
+bool act_storage_bf16(torch::Tensor spec, long li, long M, long gemm_prec,
+                      at::ScalarType dtype) {
+  TORCH_CHECK(spec.device().is_cpu() && spec.dim() == 2 &&
+                  spec.size(1) == SP_NCOLS,
+              "spec must be a CPU [nl, 7] tensor");
+  const auto sp = spec.accessor<long, 2>();
+  const long nl = spec.size(0);
+  if (gemm_prec != 1 || dtype != torch::kFloat) return false;
+  if (li < 0 || li >= nl - 1) return false;  // the last layer stays fp32
+  if (sp[li][SP_KIND] != 0 || sp[li + 1][SP_KIND] != 0) return false;
+  const long in = sp[li][SP_IN_DIM], out = sp[li][SP_OUT_DIM],
+             act = sp[li][SP_ACT], out2 = sp[li + 1][SP_OUT_DIM];
+  // relu / none need no z; sin_relu only where the engine keeps no Z
+  // stash for it (z recomputed from an in_dim <= 4 input)
+  if (!(act == ACT_RELU || act == ACT_NONE ||
+        (act == ACT_SIN_RELU && in <= 4))) {
+    return false;
+  }
+  if (out % 8 != 0) return false;
+  // producer: act_fwd_k (a bf16 input has in % 8 == 0 by this same
+  // rule one layer down) or encode_bf16_k
+  if (!fwd_mfma_shape(M, in, out) && !fwd_encode_shape(M, in, out)) {
+    return false;
+  }
+  // consumers: the next layer's forward, dW and dX on the bf16 MFMA
+  return fwd_mfma_shape(M, out, out2) && dx_mfma_shape(M, out, out2) &&
+         dw_mfma_shape(M, out, out2);
+}
+
 // fuse (trailing, default 0): 1 = run a chain that mlp_fwd_fusable
 // accepts as the optional gather plus ONE mlp_fwd_fused launch; any
 // other chain, and fuse = 0, run the layered loop below unchanged. An
@@ -2695,6 +2872,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("theta"), py::arg("grad"), py::arg("loss"),
           py::arg("loss_kind"), py::arg("loss_scale"), py::arg("M"),
           py::arg("max_blocks") = 0);
+  mod.def("act_storage_bf16", &act_storage_bf16, py::arg("spec"),
+          py::arg("li"), py::arg("M"), py::arg("gemm_prec"),
+          py::arg("dtype"));
   mod.def("bwd_chain", &bwd_chain, py::arg("spec"), py::arg("scales"),
           py::arg("xb"), py::arg("theta"), py::arg("grad"),
           py::arg("acts"), py::arg("zs"), py::arg("dzs"),

@@ -424,6 +424,41 @@ def resolve_fused_train(conf, dtype, gemm_prec, env=None) -> bool:
     return on
 
 
+def resolve_activation_storage(conf, dtype, gemm_prec, fused_fwd,
+                               fused_train, env=None) -> bool:
+    """Whether hidden activations may be stored as bf16
+    (ops/hip/gemm_bf16_act.hip), from the problem config's
+    ``activation_storage`` key: "fp32" (default) or "bf16", which needs
+    the bf16 operands of ``gemm_precision: bf16`` and excludes
+    ``fused_forward`` / ``fused_train``, whose kernels stash or skip
+    these buffers. Where the config does not set the key,
+    ``NDTA_ACT_BF16=1`` in ``env`` turns it on under bf16 operands (same
+    exclusion) and is ignored otherwise. Which layers then store bf16 is
+    ext.act_storage_bf16's decision."""
+    env = os.environ if env is None else env
+    bf16 = gemm_prec == 1 and dtype == torch.float32
+    if "activation_storage" not in conf:
+        on = bf16 and env.get("NDTA_ACT_BF16", "0") == "1"
+    else:
+        mode = conf["activation_storage"]
+        if mode not in ("fp32", "bf16"):
+            raise ValueError(
+                f"activation_storage must be 'fp32' or 'bf16', got {mode!r}"
+            )
+        on = mode == "bf16"
+        if on and not bf16:
+            raise ValueError(
+                "activation_storage: bf16 stores what the bf16 operands "
+                "read and needs gemm_precision: bf16"
+            )
+    if on and (fused_fwd or fused_train):
+        raise ValueError(
+            "activation_storage: bf16 cannot be combined with "
+            "fused_forward or fused_train"
+        )
+    return on
+
+
 class StackedEngine:
     def __init__(self, problem):
         self.ext = get_ext()
@@ -446,6 +481,11 @@ class StackedEngine:
             problem.conf, self.dtype, self.gemm_prec
         )
         self._fused_train_ok = None
+        # hidden activations as bf16 where every consumer rounds them
+        self.act_bf16 = resolve_activation_storage(
+            problem.conf, self.dtype, self.gemm_prec, self.fused_fwd,
+            self.fused_train,
+        )
 
         self.local_nodes = problem.local_nodes
         self.L = len(self.local_nodes)
@@ -569,11 +609,19 @@ class StackedEngine:
             )
         )
         last = self.spec.layers[-1]
-        for layer in self.spec.layers:
-            acts.append(
-                None if infer and layer is not last
-                else mk(layer.out_elems)
-            )
+        for li, layer in enumerate(self.spec.layers):
+            if self.act_bf16 and self.ext.act_storage_bf16(
+                self._chain_meta()[0], li, M, self.gemm_prec, self.dtype
+            ):
+                acts.append(torch.empty(
+                    L * M, layer.out_elems, device=self.device,
+                    dtype=torch.bfloat16,
+                ))
+            else:
+                acts.append(
+                    None if infer and layer is not last
+                    else mk(layer.out_elems)
+                )
             # sin_relu needs z in backward, but for a tiny in_dim the
             # dx epilogue RECOMPUTES it (4 flops) instead of storing /
             # re-reading an [L*M, out] tensor (kernel z-recompute mode)

@@ -17,6 +17,7 @@
 #include "fused_mnist.hip"
 #include "ppo_fused.hip"
 #include "mlp_grad_fused.hip"
+#include "eval.hip"
 
 #include <ATen/hip/HIPContext.h>
 
@@ -2403,6 +2404,124 @@ void mlp_fwd_fused(torch::Tensor spec, torch::Tensor scales,
   HIP_CHECK_LAST();
 }
 
+// ---- MNIST validation in one launch (eval.hip) ------------------------
+// evalk_plan is the one place that decides whether mnist_eval_k takes a
+// shape and lays out the block's LDS: x0 [R][XS], the two W1 stage
+// buffers (which the image groups and the tail alias), the conv weights
+// and bias. R = 32 where that fits the CU's 160 KB, else 16, else the
+// shape is not fusable. mnist_eval_fusable answers from it and
+// mnist_eval launches from it.
+struct EvalPlan {
+  std::string why;  // empty: fusable
+  evalk::Plan prog = {};
+  long lds = 0;
+};
+
+EvalPlan evalk_plan(long F, long K, long H, long C, long IMG, long V,
+                    long Bv, at::ScalarType dtype) {
+  EvalPlan pl;
+  if (dtype != torch::kFloat && dtype != torch::kDouble) {
+    pl.why = "dtype must be float32 or float64";
+  } else if (IMG != evalk::IMG) {
+    pl.why = "images must be 28x28";
+  } else if (K < 1 || K > 7) {
+    pl.why = "conv kernel size must be in [1, 7]";
+  } else if (F < 1 || F > 4096) {
+    pl.why = "conv filters must be in [1, 4096]";
+  } else if (H < 1 || H > 64 || C < 1 || C > 16) {
+    pl.why = "needs 1 <= H <= 64 and 1 <= C <= 16";
+  } else if (V < 1 || V > (1L << 30) || Bv < 1 || Bv > (1L << 30)) {
+    pl.why = "needs 1 <= V, Bv <= 2^30";
+  }
+  if (!pl.why.empty()) return pl;
+  evalk::Plan& pg = pl.prog;
+  const long P = (IMG - (K - 1)) / 2;
+  pg.F = (int)F; pg.K = (int)K; pg.P = (int)P; pg.I = (int)(F * P * P);
+  pg.H = (int)H; pg.C = (int)C;
+  pg.XS = evalk::x0_stride(pg.I);
+  const long esz = dtype == torch::kDouble ? 8 : 4;
+  const long wgt = (F * K * K + F + 1) / 2 * 2;
+  for (int R : {32, 16}) {
+    pg.R = R;
+    pg.off_stage = R * pg.XS;
+    pg.off_wgt = pg.off_stage + evalk::STAGE;
+    pl.lds = (pg.off_wgt + wgt) * esz;
+    if (pl.lds <= 160 * 1024) return pl;
+  }
+  pl.why = "a 16-row x0 tile does not fit the 160 KB of LDS";
+  return pl;
+}
+
+bool mnist_eval_fusable(long F, long K, long H, long C, long IMG, long V,
+                        long Bv, at::ScalarType dtype) {
+  return evalk_plan(F, K, H, C, IMG, V, Bv, dtype).why.empty();
+}
+
+// X_val [V, IMG*IMG] and y_val [V] (int64) are shared by all L nodes of
+// theta [L, n]; correct [L, V] (bool or uint8) and loss_sum [L] are
+// overwritten. loss_sum[l] is the sum over chunks of Bv rows of the
+// chunk-mean NLL, whatever the kernel's own tiling.
+void mnist_eval(torch::Tensor X_val, torch::Tensor y_val,
+                torch::Tensor theta, torch::Tensor correct,
+                torch::Tensor loss_sum, long cw_off, long cb_off,
+                long w1_off, long b1_off, long w2_off, long b2_off, long F,
+                long K, long H, long C, long IMG, long V, long Bv) {
+  CHECK_DEV(X_val); CHECK_DEV(y_val); CHECK_DEV(theta); CHECK_DEV(correct);
+  CHECK_DEV(loss_sum);
+  EvalPlan pl = evalk_plan(F, K, H, C, IMG, V, Bv, theta.scalar_type());
+  TORCH_CHECK(pl.why.empty(), "mnist_eval: ", pl.why,
+              " (mnist_eval_fusable decides)");
+  evalk::Plan& pg = pl.prog;
+  TORCH_CHECK(theta.dim() == 2, "mnist_eval: theta must be [L, n]");
+  const long L = theta.size(0), n = theta.size(1);
+  TORCH_CHECK(L >= 1 && L <= 65535, "mnist_eval: 1 <= L <= 65535");
+  TORCH_CHECK(X_val.scalar_type() == theta.scalar_type() &&
+                  loss_sum.scalar_type() == theta.scalar_type() &&
+                  X_val.numel() == V * IMG * IMG && loss_sum.numel() == L,
+              "mnist_eval: X_val must be [V, IMG*IMG] and loss_sum [L], "
+              "both of theta's dtype");
+  TORCH_CHECK(y_val.scalar_type() == torch::kLong && y_val.numel() == V,
+              "mnist_eval: y_val must be int64 [V]");
+  TORCH_CHECK(correct.element_size() == 1 && correct.numel() == L * V,
+              "mnist_eval: correct must be bool or uint8 [L, V]");
+  const long I = pg.I;
+  auto inside = [&](long off, long len) {
+    return off >= 0 && off + len <= n;
+  };
+  TORCH_CHECK(inside(cw_off, F * K * K) && inside(cb_off, F) &&
+                  inside(w1_off, H * I) && inside(b1_off, H) &&
+                  inside(w2_off, C * H) && inside(b2_off, C),
+              "mnist_eval: a layer lies outside the stack");
+  pg.cw_off = cw_off; pg.cb_off = cb_off; pg.w1_off = w1_off;
+  pg.b1_off = b1_off; pg.w2_off = w2_off; pg.b2_off = b2_off;
+  const long tiles = (V + pg.R - 1) / pg.R;
+  // part [L, tiles] in the slab bytes, one ticket per node: the fc
+  // block's workspace, whose launches leave their tickets zero as well
+  FcSplitWs& ws = fc_split_ws(theta, L * tiles, L);
+  DISPATCH_FT(theta, {
+    dispatch_kmax(K, [&](auto kmax) {
+      auto kern = evalk::mnist_eval_k<scalar_t, decltype(kmax)::value>;
+      static bool lds_raised = false;  // once per variant: > 64 KB of LDS
+      if (!lds_raised) {
+        TORCH_CHECK(hipFuncSetAttribute(
+                        reinterpret_cast<const void*>(kern),
+                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                        160 * 1024) == hipSuccess,
+                    "mnist_eval: cannot raise the dynamic LDS limit");
+        lds_raised = true;
+      }
+      hipLaunchKernelGGL(kern, dim3(tiles, L), dim3(256), (size_t)pl.lds,
+          cur_stream(), X_val.data_ptr<scalar_t>(),
+          y_val.data_ptr<long>(), theta.data_ptr<scalar_t>(),
+          static_cast<unsigned char*>(correct.data_ptr()),
+          loss_sum.data_ptr<scalar_t>(),
+          reinterpret_cast<scalar_t*>(ws.slabs.data_ptr()),
+          ws.tickets.data_ptr<int>(), pg, n, (int)V, (int)Bv);
+    });
+  });
+  HIP_CHECK_LAST();
+}
+
 // ---- whole gradient row in one launch (mlp_grad_fused.hip) ------------
 // mlp_grad_plan is the one place that decides whether mlp_grad_fused_k
 // takes a chain and lays out its LDS: what mlp_plan accepts, narrowed to
@@ -2872,6 +2991,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("theta"), py::arg("grad"), py::arg("loss"),
           py::arg("loss_kind"), py::arg("loss_scale"), py::arg("M"),
           py::arg("max_blocks") = 0);
+  mod.def("mnist_eval_fusable", &mnist_eval_fusable, py::arg("F"),
+          py::arg("K"), py::arg("H"), py::arg("C"), py::arg("IMG"),
+          py::arg("V"), py::arg("Bv"), py::arg("dtype"));
+  mod.def("mnist_eval", &mnist_eval, py::arg("X_val"), py::arg("y_val"),
+          py::arg("theta"), py::arg("correct"), py::arg("loss_sum"),
+          py::arg("cw_off"), py::arg("cb_off"), py::arg("w1_off"),
+          py::arg("b1_off"), py::arg("w2_off"), py::arg("b2_off"),
+          py::arg("F"), py::arg("K"), py::arg("H"), py::arg("C"),
+          py::arg("IMG"), py::arg("V"), py::arg("Bv"));
   mod.def("act_storage_bf16", &act_storage_bf16, py::arg("spec"),
           py::arg("li"), py::arg("M"), py::arg("gemm_prec"),
           py::arg("dtype"));

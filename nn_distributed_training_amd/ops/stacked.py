@@ -459,6 +459,25 @@ def resolve_activation_storage(conf, dtype, gemm_prec, fused_fwd,
     return on
 
 
+def resolve_fused_validation(conf, env=None) -> bool:
+    """Whether validate_all() asks for the one-launch validation kernel
+    (ops/hip/eval.hip), from the problem config's ``fused_validation``
+    key: false (default) or true. Where the config does not set the key,
+    ``NDTA_FUSED_VAL=1`` in ``env`` turns it on. The kernel runs in the
+    engine's native precision whatever ``gemm_precision`` says; a model
+    or shape it cannot take (ext.mnist_eval_fusable) is validated
+    layered whatever the flag."""
+    env = os.environ if env is None else env
+    if "fused_validation" not in conf:
+        return env.get("NDTA_FUSED_VAL", "0") == "1"
+    on = conf["fused_validation"]
+    if not isinstance(on, bool):
+        raise ValueError(
+            f"fused_validation must be true or false, got {on!r}"
+        )
+    return on
+
+
 class StackedEngine:
     def __init__(self, problem):
         self.ext = get_ext()
@@ -486,6 +505,9 @@ class StackedEngine:
             problem.conf, self.dtype, self.gemm_prec, self.fused_fwd,
             self.fused_train,
         )
+
+        # one-launch validation where the model and shape are fusable
+        self.fused_val = resolve_fused_validation(problem.conf)
 
         self.local_nodes = problem.local_nodes
         self.L = len(self.local_nodes)
@@ -1116,6 +1138,46 @@ class StackedEngine:
         self._val_pack = None
         return self._val
 
+    def _fused_val_applicable(self, V, Bv):
+        """fused_validation is on and ext.mnist_eval takes this model:
+        conv_pool(relu) -> linear(relu) -> linear(logsoftmax) of a
+        classification problem on the GPU, at a shape its plan accepts."""
+        if not (self.fused_val and self.device.type == "cuda"
+                and self.classification):
+            return False
+        ls = self.spec.layers
+        return (
+            len(ls) == 3
+            and ls[0].kind == "conv_pool"
+            and getattr(ls[0], "activation", "relu") == "relu"
+            and ls[1].kind == "linear" and ls[1].activation == "relu"
+            and ls[2].kind == "linear"
+            and ls[2].activation == "logsoftmax"
+            and ls[1].in_dim == ls[0].out_elems
+            and ls[2].in_dim == ls[1].out_dim
+            and self.ext.mnist_eval_fusable(
+                ls[0].out_dim, ls[0].kernel_size, ls[1].out_dim,
+                ls[2].out_dim, ls[0].in_dim, V, Bv, self.dtype,
+            )
+        )
+
+    def _validate_fused(self, xd, yd, V, Bv):
+        """validate_all's classification triple from one launch: the
+        staged [V, 784] images are read by every node, and the chunk
+        means of val_batch_size rows are folded inside the kernel."""
+        conv, fc1, fc2 = self.spec.layers
+        correct = torch.empty(
+            self.L, V, device=self.device, dtype=torch.bool
+        )
+        loss_sum = torch.empty(self.L, device=self.device, dtype=self.dtype)
+        self.ext.mnist_eval(
+            xd, yd, self.theta, correct, loss_sum, conv.w_off, conv.b_off,
+            fc1.w_off, fc1.b_off, fc2.w_off, fc2.b_off, conv.out_dim,
+            conv.kernel_size, fc1.out_dim, fc2.out_dim, conv.in_dim, V, Bv,
+        )
+        acc = correct.sum(dim=1).to(self.dtype) / V
+        return loss_sum.cpu() / V, acc.cpu(), correct.cpu()
+
     def validate_all(self):
         """Per-node validation on the shared val set.
 
@@ -1130,6 +1192,8 @@ class StackedEngine:
         xd, yd = self._stage_val()
         V = xd.shape[0]
         Bv = min(int(pr.conf.get("val_batch_size", 1024)), V)
+        if self._fused_val_applicable(V, Bv):
+            return self._validate_fused(xd, yd, V, Bv)
         if self._val_pack is None or self._val_pack["M"] != Bv:
             self._val_pack = self._alloc_bufs(M=Bv, train=False)
         pack = self._val_pack

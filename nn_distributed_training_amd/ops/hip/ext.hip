@@ -18,6 +18,7 @@
 #include "ppo_fused.hip"
 #include "mlp_grad_fused.hip"
 #include "eval.hip"
+#include "mlp_eval.hip"
 
 #include <ATen/hip/HIPContext.h>
 
@@ -2522,6 +2523,165 @@ void mnist_eval(torch::Tensor X_val, torch::Tensor y_val,
   HIP_CHECK_LAST();
 }
 
+// ---- density-MLP validation in one launch (mlp_eval.hip) --------------
+// mlp_eval_plan is the one place that decides whether mlp_eval_k takes a
+// chain and lays out the block's LDS: the wide image [R][ldw], the two
+// narrow images [R][66], the two W stages, the inputs and the row
+// losses. R is 64 (float) / 32 (double); at the widest chain the layout
+// is 118,528 B / 135,936 B, so every chain inside the limits fits the
+// CU's 160 KB. loss_kind 0 is predict mode, 1 BCE, 2 MSE, 3 L1.
+// mlp_eval_fusable answers from it and mlp_eval launches from it.
+struct MlpEvalPlan {
+  std::string why;  // empty: fusable
+  mlpe::Plan prog = {};
+  long lds = 0;
+};
+
+MlpEvalPlan mlp_eval_plan(const torch::Tensor& spec, long V, long Bv,
+                          long loss_kind, at::ScalarType dtype) {
+  TORCH_CHECK(spec.device().is_cpu() && spec.dim() == 2 &&
+                  spec.size(1) == SP_NCOLS &&
+                  spec.scalar_type() == torch::kLong,
+              "spec must be a CPU int64 [nl, 7] tensor");
+  MlpEvalPlan pl;
+  const auto sp = spec.accessor<long, 2>();
+  const long nl = spec.size(0);
+  if (dtype != torch::kFloat && dtype != torch::kDouble) {
+    pl.why = "dtype must be float32 or float64";
+  } else if (nl < 2 || nl > mlpe::MAXL) {
+    pl.why = "needs 2..8 linear layers";
+  } else if (V < 1 || V > (1L << 30) || Bv < 1 || Bv > (1L << 30)) {
+    pl.why = "needs 1 <= V, Bv <= 2^30";
+  } else if (loss_kind < 0 || loss_kind > 3) {
+    pl.why = "loss_kind must be 0 (predict), 1 (BCE), 2 (MSE) or 3 (L1)";
+  } else if (loss_kind != 0 && sp[nl - 1][SP_OUT_DIM] != 1) {
+    pl.why = "a loss needs a head of width 1";
+  }
+  mlpe::Plan& pg = pl.prog;
+  for (long li = 0; li < nl && pl.why.empty(); ++li) {
+    const long in = sp[li][SP_IN_DIM], out = sp[li][SP_OUT_DIM],
+               act = sp[li][SP_ACT];
+    const bool lift = li == 0, tail = li == nl - 1;
+    if (sp[li][SP_KIND] != 0 || in < 1 || out < 1 ||
+        (li > 0 && in != sp[li - 1][SP_OUT_DIM])) {
+      pl.why = "needs linear layers, each fed by the one below";
+    } else if (lift && (in > mlpe::LIFT_IN ||
+                        out > (nl == 2 ? mlpe::NARROW : mlpe::WIDE))) {
+      pl.why = "first layer needs in <= 4 and out <= 256 (64 before the "
+               "last)";
+    } else if (!lift && !tail && out > mlpe::NARROW) {
+      pl.why = "a hidden layer above the first needs out <= 64";
+    } else if (tail && out > mlpe::TAIL_OUT) {
+      pl.why = "last layer needs out <= 4";
+    } else if (tail ? !(act == ACT_NONE || act == ACT_SIGMOID ||
+                        act == ACT_TANH)
+                    : !mlp_act_ok(act, lift)) {
+      pl.why = "an activation the kernel does not have";
+    }
+    pg.ly[li] = {sp[li][SP_W_OFF], sp[li][SP_B_OFF], (int)in, (int)out,
+                 (int)act};
+  }
+  if (!pl.why.empty()) return pl;
+  const long R = dtype == torch::kDouble ? 16 * mlpe::frags<double>()
+                                         : 16 * mlpe::frags<float>();
+  const int out0 = pg.ly[0].out;
+  pg.nl = (int)nl;
+  pg.loss_kind = (int)loss_kind;
+  pg.ldw = mlpe::wide_stride(out0);
+  pg.cp = 4;
+  while (pg.cp < out0) pg.cp *= 2;
+  pg.off_nar = (int)(R * pg.ldw);
+  pg.off_stage = pg.off_nar + (int)(2 * R * mlpe::NLD);
+  pg.off_x = pg.off_stage + mlpe::STAGE;
+  pg.off_rl = pg.off_x + (int)(R * mlpe::LIFT_IN);
+  pl.lds = (pg.off_rl + R) * (dtype == torch::kDouble ? 8 : 4);
+  return pl;
+}
+
+bool mlp_eval_fusable(torch::Tensor spec, long V, long Bv, long loss_kind,
+                      at::ScalarType dtype) {
+  return mlp_eval_plan(spec, V, Bv, loss_kind, dtype).why.empty();
+}
+
+// X_val [V, in] is shared by all L nodes of theta [L, n]. Loss mode
+// (loss_kind 1..3): y_val [V] and loss_sum [L]; loss_sum[l] is
+// overwritten with the sum over chunks of Bv rows of the chunk-mean
+// loss, whatever the kernel's own tiling. Predict mode (loss_kind 0):
+// yhat [L, V, out] is overwritten.
+void mlp_eval(torch::Tensor spec, torch::Tensor scales, torch::Tensor X_val,
+              c10::optional<torch::Tensor> y_val, torch::Tensor theta,
+              c10::optional<torch::Tensor> loss_sum,
+              c10::optional<torch::Tensor> yhat, long V, long Bv,
+              long loss_kind) {
+  CHECK_DEV(X_val); CHECK_DEV(theta);
+  MlpEvalPlan pl =
+      mlp_eval_plan(spec, V, Bv, loss_kind, theta.scalar_type());
+  TORCH_CHECK(pl.why.empty(), "mlp_eval: ", pl.why,
+              " (mlp_eval_fusable decides)");
+  mlpe::Plan& pg = pl.prog;
+  TORCH_CHECK(theta.dim() == 2, "mlp_eval: theta must be [L, n]");
+  const long L = theta.size(0), n = theta.size(1);
+  TORCH_CHECK(L >= 1 && L <= 65535, "mlp_eval: 1 <= L <= 65535");
+  TORCH_CHECK(scales.device().is_cpu() && scales.numel() == pg.nl &&
+                  scales.scalar_type() == torch::kDouble,
+              "mlp_eval: scales needs one float64 entry per layer");
+  pg.scale = scales.accessor<double, 1>()[0];
+  const auto dt = theta.scalar_type();
+  TORCH_CHECK(X_val.scalar_type() == dt &&
+                  X_val.numel() == V * pg.ly[0].in,
+              "mlp_eval: X_val must be [V, in] of theta's dtype");
+  for (int li = 0; li < pg.nl; ++li) {
+    const mlpe::Layer& y = pg.ly[li];
+    TORCH_CHECK(y.w_off >= 0 && y.b_off >= 0 &&
+                    y.w_off + (long)y.in * y.out <= n &&
+                    y.b_off + y.out <= n,
+                "mlp_eval: layer ", li, " lies outside the stack");
+  }
+  const bool predict = loss_kind == 0;
+  const long out = pg.ly[pg.nl - 1].out;
+  auto given = [&](const c10::optional<torch::Tensor>& t, long numel) {
+    return t.has_value() && t->is_cuda() && t->is_contiguous() &&
+           t->scalar_type() == dt && t->numel() == numel;
+  };
+  if (predict) {
+    TORCH_CHECK(!y_val.has_value() && !loss_sum.has_value() &&
+                    given(yhat, L * V * out),
+                "mlp_eval: predict mode takes yhat [L, V, out] of theta's "
+                "dtype and neither y_val nor loss_sum");
+  } else {
+    TORCH_CHECK(given(y_val, V) && given(loss_sum, L) && !yhat.has_value(),
+                "mlp_eval: loss mode takes y_val [V] and loss_sum [L] of "
+                "theta's dtype and no yhat");
+  }
+  const long R = dt == torch::kDouble ? 16 * mlpe::frags<double>()
+                                      : 16 * mlpe::frags<float>();
+  const long tiles = (V + R - 1) / R;
+  // part [L, tiles] in the slab bytes, one ticket per node: the fc
+  // block's workspace, as mnist_eval
+  FcSplitWs& ws = fc_split_ws(theta, L * tiles, L);
+  DISPATCH_FT(theta, {
+    auto kern = mlpe::mlp_eval_k<scalar_t>;
+    static bool lds_raised = false;  // once per variant: > 64 KB of LDS
+    if (!lds_raised) {
+      TORCH_CHECK(hipFuncSetAttribute(
+                      reinterpret_cast<const void*>(kern),
+                      hipFuncAttributeMaxDynamicSharedMemorySize,
+                      160 * 1024) == hipSuccess,
+                  "mlp_eval: cannot raise the dynamic LDS limit");
+      lds_raised = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(tiles, L), dim3(256), (size_t)pl.lds,
+        cur_stream(), X_val.data_ptr<scalar_t>(),
+        predict ? nullptr : y_val->data_ptr<scalar_t>(),
+        theta.data_ptr<scalar_t>(),
+        predict ? nullptr : loss_sum->data_ptr<scalar_t>(),
+        predict ? yhat->data_ptr<scalar_t>() : nullptr,
+        reinterpret_cast<scalar_t*>(ws.slabs.data_ptr()),
+        ws.tickets.data_ptr<int>(), pg, n, (int)V, (int)Bv);
+  });
+  HIP_CHECK_LAST();
+}
+
 // ---- whole gradient row in one launch (mlp_grad_fused.hip) ------------
 // mlp_grad_plan is the one place that decides whether mlp_grad_fused_k
 // takes a chain and lays out its LDS: what mlp_plan accepts, narrowed to
@@ -3000,6 +3160,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("b1_off"), py::arg("w2_off"), py::arg("b2_off"),
           py::arg("F"), py::arg("K"), py::arg("H"), py::arg("C"),
           py::arg("IMG"), py::arg("V"), py::arg("Bv"));
+  mod.def("mlp_eval_fusable", &mlp_eval_fusable, py::arg("spec"),
+          py::arg("V"), py::arg("Bv"), py::arg("loss_kind"),
+          py::arg("dtype"));
+  mod.def("mlp_eval", &mlp_eval, py::arg("spec"), py::arg("scales"),
+          py::arg("X_val"), py::arg("y_val"), py::arg("theta"),
+          py::arg("loss_sum"), py::arg("yhat"), py::arg("V"),
+          py::arg("Bv"), py::arg("loss_kind"));
   mod.def("act_storage_bf16", &act_storage_bf16, py::arg("spec"),
           py::arg("li"), py::arg("M"), py::arg("gemm_prec"),
           py::arg("dtype"));

@@ -99,6 +99,9 @@ ACT_IDS = {
     "logsoftmax": 5,
 }
 
+# ext.mlp_eval's loss_kind of a regression loss (0 is its predict mode)
+_MLP_EVAL_LOSS = {"BCELoss": 1, "MSELoss": 2, "L1Loss": 3}
+
 
 def _dataset_tensors(ds):
     """(inputs [N, ...], targets [N]) for TensorDataset/Subset trees."""
@@ -461,12 +464,13 @@ def resolve_activation_storage(conf, dtype, gemm_prec, fused_fwd,
 
 def resolve_fused_validation(conf, env=None) -> bool:
     """Whether validate_all() asks for the one-launch validation kernel
-    (ops/hip/eval.hip), from the problem config's ``fused_validation``
+    (ops/hip/eval.hip for the MNIST conv net, ops/hip/mlp_eval.hip for
+    the regression MLPs), from the problem config's ``fused_validation``
     key: false (default) or true. Where the config does not set the key,
     ``NDTA_FUSED_VAL=1`` in ``env`` turns it on. The kernel runs in the
     engine's native precision whatever ``gemm_precision`` says; a model
-    or shape it cannot take (ext.mnist_eval_fusable) is validated
-    layered whatever the flag."""
+    or shape it cannot take (ext.mnist_eval_fusable,
+    ext.mlp_eval_fusable) is validated layered whatever the flag."""
     env = os.environ if env is None else env
     if "fused_validation" not in conf:
         return env.get("NDTA_FUSED_VAL", "0") == "1"
@@ -1141,10 +1145,14 @@ class StackedEngine:
     def _fused_val_applicable(self, V, Bv):
         """fused_validation is on and ext.mnist_eval takes this model:
         conv_pool(relu) -> linear(relu) -> linear(logsoftmax) of a
-        classification problem on the GPU, at a shape its plan accepts."""
-        if not (self.fused_val and self.device.type == "cuda"
-                and self.classification):
+        classification problem on the GPU, at a shape its plan accepts.
+        For a regression problem: ext.mlp_eval takes the chain and the
+        loss (ext.mlp_eval_fusable)."""
+        if not (self.fused_val and self.device.type == "cuda"):
             return False
+        if not self.classification:
+            kind = _MLP_EVAL_LOSS.get(self._loss_kind, 0)
+            return kind != 0 and self._mlp_eval_ok(V, Bv, kind)
         ls = self.spec.layers
         return (
             len(ls) == 3
@@ -1178,6 +1186,49 @@ class StackedEngine:
         acc = correct.sum(dim=1).to(self.dtype) / V
         return loss_sum.cpu() / V, acc.cpu(), correct.cpu()
 
+    def _mlp_eval_ok(self, V, Bv, loss_kind):
+        return self.ext.mlp_eval_fusable(
+            self._chain_meta()[0], V, Bv, loss_kind, self.dtype
+        )
+
+    def _validate_mlp_fused(self, xd, yd, V, Bv):
+        """validate_all's regression losses [L] from one launch: every
+        node reads the staged [V, in] inputs, no activation leaves the
+        CU, and the chunk means are folded inside the kernel."""
+        spec_t, scales_t = self._chain_meta()
+        loss_sum = torch.empty(self.L, device=self.device, dtype=self.dtype)
+        self.ext.mlp_eval(
+            spec_t, scales_t, xd, yd.reshape(-1), self.theta, loss_sum,
+            None, V, Bv, _MLP_EVAL_LOSS[self._loss_kind],
+        )
+        return loss_sum.cpu()
+
+    def predict_all(self, x):
+        """Every local node's model on the rows of x [P, in]: [L, P, out]
+        in the engine's dtype, from ext.mlp_eval's predict mode. Only
+        where fused_validation is on and the chain is fusable
+        (predict_all_applicable)."""
+        P = x.shape[0]
+        spec_t, scales_t = self._chain_meta()
+        xd = x.reshape(P, -1).to(self.device, self.dtype).contiguous()
+        yhat = torch.empty(
+            self.L, P, self.spec.layers[-1].out_dim,
+            device=self.device, dtype=self.dtype,
+        )
+        self.ext.mlp_eval(
+            spec_t, scales_t, xd, None, self.theta, None, yhat, P, 1, 0
+        )
+        return yhat
+
+    def predict_all_applicable(self, P):
+        """fused_validation is on and ext.mlp_eval's predict mode takes
+        this regression model on the GPU."""
+        return bool(
+            self.fused_val and self.device.type == "cuda"
+            and not self.classification and P >= 1
+            and self._mlp_eval_ok(P, 1, 0)
+        )
+
     def validate_all(self):
         """Per-node validation on the shared val set.
 
@@ -1193,6 +1244,8 @@ class StackedEngine:
         V = xd.shape[0]
         Bv = min(int(pr.conf.get("val_batch_size", 1024)), V)
         if self._fused_val_applicable(V, Bv):
+            if not self.classification:
+                return self._validate_mlp_fused(xd, yd, V, Bv)
             return self._validate_fused(xd, yd, V, Bv)
         if self._val_pack is None or self._val_pack["M"] != Bv:
             self._val_pack = self._alloc_bufs(M=Bv, train=False)

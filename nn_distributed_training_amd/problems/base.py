@@ -171,6 +171,18 @@ class ProblemBase:
             full = full.to(torch.bool)
         return full.reshape(self.N, *tail).cpu()
 
+    def mesh_grid_density_all(self):
+        """Every local node's density on ``self.mesh_inputs``, stacked
+        [L, P, out]. One launch of the stacked engine's predict mode
+        where ``fused_validation`` is on and the model is fusable
+        (StackedEngine.predict_all_applicable); else None, and the
+        caller evaluates its eager modules node by node as before."""
+        eng = self.stacked
+        x = self.mesh_inputs
+        if eng is None or not eng.predict_all_applicable(x.shape[0]):
+            return None
+        return eng.predict_all(x).to(torch.get_default_dtype())
+
     # ------------------------------------------------------------------
     def save_metrics(self, output_dir):
         if not self.is_root:

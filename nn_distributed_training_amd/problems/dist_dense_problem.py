@@ -78,6 +78,10 @@ class DistDensityProblem(ProblemBase):
                     val_losses.amin().item(), val_losses.amax().item()
                 )
             elif met_name == "mesh_grid_density":
+                fused = self.mesh_grid_density_all()
+                if fused is not None:
+                    self.metrics[met_name].append(fused.cpu())
+                    continue
                 dens = [
                     self.mesh_grid_density(i) for i in self.local_nodes
                 ]

@@ -202,17 +202,20 @@ class DistOnlineDensityProblem(ProblemBase):
             elif met_name == "mesh_grid_density":
                 mc = self.conf["metrics_config"]
                 if (not mc.get("mesh_only_at_end", False)) or at_end:
-                    dens = [
-                        self.mesh_grid_density(i) for i in self.local_nodes
-                    ]
-                    loc = (
-                        torch.stack(dens)
-                        if dens
-                        else torch.zeros(
-                            0, *self.mesh_inputs.shape[:1], 1,
-                            device=self.device,
+                    loc = self.mesh_grid_density_all()
+                    if loc is None:
+                        dens = [
+                            self.mesh_grid_density(i)
+                            for i in self.local_nodes
+                        ]
+                        loc = (
+                            torch.stack(dens)
+                            if dens
+                            else torch.zeros(
+                                0, *self.mesh_inputs.shape[:1], 1,
+                                device=self.device,
+                            )
                         )
-                    )
                     # gather so rank 0 (the saver) has every node's mesh
                     self.metrics[met_name].append(
                         self.gather_per_node_rows(loc)

@@ -1,13 +1,17 @@
-"""Time validate_all() of the MNIST engine, layered vs one launch.
+"""Time validate_all() of the stacked engine, layered vs one launch.
 
 Stand-alone measurement (not a test, not part of bench.py) at the paper
-shape: 10 nodes on a cycle graph, MNISTConvNet(3, 5, 64), V = 10,000
-synthetic validation images, val_batch_size 128, in fp64 and fp32. Two
-comparisons on the same seeded data and parameters:
+shapes, in fp64 and fp32. --workload mnist: 10 nodes on a cycle graph,
+MNISTConvNet(3, 5, 64), V = 10,000 synthetic validation images,
+val_batch_size 128, DiNNO rounds. --workload density: bench.py's online
+density problem with 8 nodes, FourierNet [2, 256, 64, 64, 64, 1] scale
+0.05, 200 validation scans of 20 beams x 25 samples (V = 100,000),
+val_batch_size 10,000, DSGT rounds. Two comparisons on the same seeded
+data and parameters:
 
 * one validate_all() call with fused_validation off (the layered path,
-  the comparison) and on (ops/hip/eval.hip);
-* one evaluation period of a DiNNO run with evaluate_frequency 20:
+  the comparison) and on (ops/hip/eval.hip, ops/hip/mlp_eval.hip);
+* one evaluation period of a run with evaluate_frequency 20:
   --rounds (20) step_round calls alone against the same rounds plus one
   validate_all(), off and on. The difference over the total is the
   share of the run validation takes.
@@ -18,7 +22,8 @@ synchronize (validate_all() itself ends in a copy to the host), after
 variants alternating, and the median with the min-max spread is
 reported. Prints one JSON line per dtype.
 
-Run: python tools/bench_validation.py [--iters 50 --repeats 7]
+Run: python tools/bench_validation.py [--workload density]
+         [--iters 50 --repeats 7]
 """
 
 from __future__ import annotations
@@ -76,6 +81,57 @@ def make_driver(args, subsets, val, device, fused):
     return driver
 
 
+def make_density_driver(args, device, fused):
+    import numpy as np
+
+    from nn_distributed_training_amd.data.floorplan import (
+        synthetic_floorplan,
+        synthetic_waypoints,
+    )
+    from nn_distributed_training_amd.data.lidar import (
+        Lidar2D,
+        OnlineTrajectoryLidarDataset,
+        RandomPoseLidarDataset,
+    )
+    from nn_distributed_training_amd.models import FourierNet
+    from nn_distributed_training_amd.optimizers.dsgt import DSGT
+    from nn_distributed_training_amd.ops.stacked import DSGTStackedDriver
+    from nn_distributed_training_amd.problems.dist_online_dense_problem \
+        import DistOnlineDensityProblem
+
+    np.random.seed(0)
+    torch.manual_seed(0)
+    img = synthetic_floorplan(nx=256, ny=256, num_walls=10,
+                              border_width=24, seed=0)
+    lidar = Lidar2D(img, 20, 0.2, 25, 1.0, 50, 3)
+    subsets = [
+        OnlineTrajectoryLidarDataset(lidar, wp, 30, 100)
+        for wp in synthetic_waypoints(img, args.nodes, seed=0)
+    ]
+    val = RandomPoseLidarDataset(lidar, args.val)
+    opt_conf = {
+        "alg_name": "dsgt", "alpha": 0.001, "outer_iterations": 4000,
+        "init_grads": True, "profile": False,
+    }
+    conf = {
+        "problem_name": "bench_validation", "train_batch_size": 20000,
+        "val_batch_size": args.val_batch_size, "comm_radius": 120.0,
+        "dynamic_graph": True, "save_models": False, "data_seed": 0,
+        "verbose_evals": False, "metrics": ["validation_loss"],
+        "metrics_config": {"evaluate_frequency": 20, "tloss_decay": 0.2,
+                           "mesh_only_at_end": True},
+        "optimizer_config": opt_conf, "fused_validation": fused,
+    }
+    pr = DistOnlineDensityProblem(
+        FourierNet([2, 256, 64, 64, 64, 1], scale=0.05), torch.nn.BCELoss(),
+        subsets, val, device, conf,
+    )
+    pr.stacked = StackedEngine(pr)
+    driver = DSGTStackedDriver(DSGT(pr, device, opt_conf), pr)
+    driver.prepare()
+    return driver
+
+
 def window(fn, iters):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -103,13 +159,17 @@ def compare(fns, iters, warmup, repeats):
 def bench_dtype(dtype, args):
     torch.set_default_dtype(dtype)
     dev = torch.device("cuda")
-    subsets = split_train_set(
-        SyntheticMNIST(args.train, seed=0), args.nodes, "hetero")
-    val = SyntheticMNIST(args.val, seed=1)
-    off = make_driver(args, subsets, val, dev, False)
-    on = make_driver(args, subsets, val, dev, True)
+    if args.workload == "density":
+        off = make_density_driver(args, dev, False)
+        on = make_density_driver(args, dev, True)
+    else:
+        subsets = split_train_set(
+            SyntheticMNIST(args.train, seed=0), args.nodes, "hetero")
+        val = SyntheticMNIST(args.val, seed=1)
+        off = make_driver(args, subsets, val, dev, False)
+        on = make_driver(args, subsets, val, dev, True)
     e_off, e_on = off.pr.stacked, on.pr.stacked
-    V = len(val)
+    V = e_on._stage_val()[0].shape[0]
     assert e_on._fused_val_applicable(V, min(args.val_batch_size, V))
 
     # a few rounds first, so that the nodes differ; then the same
@@ -117,10 +177,14 @@ def bench_dtype(dtype, args):
     for k in range(3):
         off.step_round(k)
     e_on.theta.copy_(e_off.theta)
-    l0, a0, c0 = e_off.validate_all()
-    l1, a1, c1 = e_on.validate_all()
+    if args.workload == "density":  # regression: the losses [L] alone
+        l0, l1 = e_off.validate_all(), e_on.validate_all()
+        mask_diff = None
+    else:
+        l0, a0, c0 = e_off.validate_all()
+        l1, a1, c1 = e_on.validate_all()
+        mask_diff = int((c0 != c1).sum())
     loss_diff = (l0 - l1).abs().max().item()
-    mask_diff = int((c0 != c1).sum())
 
     v = compare({"off": e_off.validate_all, "on": e_on.validate_all},
                 args.iters, args.warmup, args.repeats)
@@ -146,11 +210,13 @@ def bench_dtype(dtype, args):
         return round((r[k][0] - r["rounds_only"][0]) / r[k][0], 3)
 
     out = {
+        "workload": args.workload,
         "dtype": str(dtype).replace("torch.", ""),
         "nodes": args.nodes, "V": V,
         "val_batch_size": args.val_batch_size,
         "iters": args.iters, "repeats": args.repeats,
-        "max_abs_loss_diff": loss_diff, "mask_rows_differing": mask_diff,
+        "max_abs_loss_diff": loss_diff, "max_loss": l0.abs().max().item(),
+        "mask_rows_differing": mask_diff,
         "validate_all": {k: row(x) for k, x in v.items()},
         "validate_all_speedup": round(v["off"][0] / v["on"][0], 2),
         "rounds_per_period": args.rounds,
@@ -164,16 +230,26 @@ def bench_dtype(dtype, args):
 
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    p.add_argument("--nodes", type=int, default=10)
+    p.add_argument("--workload", default="mnist",
+                   choices=["mnist", "density"])
+    p.add_argument("--nodes", type=int, default=0,
+                   help="0 = workload default (10 mnist / 8 density)")
     p.add_argument("--train", type=int, default=6000)
-    p.add_argument("--val", type=int, default=10000)
-    p.add_argument("--val-batch-size", type=int, default=128)
+    p.add_argument("--val", type=int, default=0,
+                   help="validation images (mnist, default 10000) or "
+                        "scans of 500 rows (density, default 200)")
+    p.add_argument("--val-batch-size", type=int, default=0,
+                   help="0 = workload default (128 mnist / 10000 density)")
     p.add_argument("--rounds", type=int, default=20)
     p.add_argument("--iters", type=int, default=50)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--repeats", type=int, default=7)
     p.add_argument("--dtypes", nargs="+", default=["float64", "float32"])
     args = p.parse_args(argv)
+    dens = args.workload == "density"
+    args.nodes = args.nodes or (8 if dens else 10)
+    args.val = args.val or (200 if dens else 10000)
+    args.val_batch_size = args.val_batch_size or (10000 if dens else 128)
     if not torch.cuda.is_available():
         sys.exit("bench_validation.py measures on the GPU; none found")
     for name in args.dtypes:
